@@ -18,7 +18,11 @@ features and control maps) and sends every rank ITS shard point-to-point over RC
 sent at a time; timed and reported.  weak scaling.
 
 Prints ONE JSON line (rank 0) with `roofline` (decode step vs the HBM roofline, HIP-event
-timed inside the library on its own stream) and `cpu_baseline` (the CPU oracle, N=1 only).
+timed inside the library on its own stream).  A plain run sets up, warms up, times `--steps` steps,
+writes the last step's outputs if `--dump-outputs DIR` is given, and prints that line.  `--full` adds
+what the headline figure does not need: the self-checks (twin rows, the committed golden), the VQ
+decoder timed in both arithmetics, `cpu_baseline` (the CPU oracle, N=1 only) and, on one GPU, the
+`exact` and `configs` blocks timed in child processes.
 """
 import argparse
 import json
@@ -62,6 +66,12 @@ def parse():
     ap.add_argument("--top-k", type=int, default=2000)
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed region: the self-checks (twin rows, the committed golden), the VQ decoder "
+                         "timed in both arithmetics, the CPU baseline and, on one GPU, the child legs (`exact` and `configs` blocks, the config-5 variant)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/tokens.npy and DIR/pixels.npy (float32; every value, or a fixed "
+                         "seeded sample of 7.5 M values when there are more: at most 60 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--input-dist", default="local", choices=["scatter", "local"],
                     help="N > 1: 'local' = every rank draws its own shard (per-image seeds: the same global batch for any N; no input traffic — the "
@@ -73,11 +83,11 @@ def parse():
                          "the token loop is HBM-bound and the decoder's GEMM grids take every CU; kept for experiments)")
     ap.add_argument("--cpu-tokens", type=int, default=48, help="decode tokens timed by the CPU baseline sample")
     ap.add_argument("--exact-leg-steps", type=int, default=3,
-                    help="headline configuration on one GPU only: after the timed region, time this many steps (+ 1 warm-up) of the BIT-IDENTICAL mode (`--precision fp32`, 384 "
+                    help="--full, headline configuration on one GPU only: after the timed region, time this many steps (+ 1 warm-up) of the BIT-IDENTICAL mode (`--precision fp32`, 384 "
                          "images) in a child process and report it as the `exact` block of the same JSON line — north_star asks for >= 20 images/s WITH the reference's greedy "
                          "tokens; the bf16 headline is tolerance-graded, this leg is the one whose tokens are compared with the reference's.  0 = skip")
     ap.add_argument("--config-legs", default="2,3,5,4,1",
-                    help="headline configuration on one GPU only: after the exact leg, time these BASELINE configs (`--config N`, 1 warm-up + --config-leg-steps steps each) in child "
+                    help="--full, headline configuration on one GPU only: after the exact leg, time these BASELINE configs (`--config N`, 1 warm-up + --config-leg-steps steps each) in child "
                          "processes and report them as the `configs` block of the same JSON line, so that the driver's record carries every BASELINE config, not only the headline.  '' = skip")
     ap.add_argument("--config-leg-steps", type=int, default=3)
     ap.add_argument("--legs-budget-s", type=float, default=420.0, help="stop starting further config legs once this much wall clock has gone into them")
@@ -234,9 +244,9 @@ def pack_cache_dir():
 
 
 def config_legs(args, world):
-    """The BASELINE configs timed as child legs behind the headline: only for the default headline run on ONE GPU (a multi-GPU run times the metric, nothing else:
+    """The BASELINE configs timed as child legs behind the headline: only for the `--full` headline run on ONE GPU (a multi-GPU run times the metric, nothing else:
     every rank would otherwise spawn its own children on its own device while the others wait at the barrier)."""
-    if world != 1 or args.no_variants or args.config != 0 or args.precision != "bf16" or args.model != "xl" or args.batch != 768:
+    if not args.full or world != 1 or args.no_variants or args.config != 0 or args.precision != "bf16" or args.model != "xl" or args.batch != 768:
         return []
     if args.weights_fp8 or args.kv_fp8 or args.sample_logits:
         return []
@@ -244,9 +254,10 @@ def config_legs(args, world):
 
 
 def child_leg(extra, timeout=900):
-    """One more bench configuration in a child process (its own HIP contexts: the parent has released its device memory), returns its parsed JSON line or an error."""
+    """One more bench configuration in a child process (its own HIP contexts: the parent has released its device memory), returns its parsed JSON line or an error.
+    The child runs with `--full` for its self-checks and VQ timings (the `exact` block reports its golden agreement), without legs or CPU baseline of its own."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--no-cpu-baseline", "--no-variants", "--exact-leg-steps", "0"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--no-cpu-baseline", "--no-variants", "--exact-leg-steps", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
@@ -256,6 +267,23 @@ def child_leg(extra, timeout=900):
         return json.loads(line[-1])
     except Exception as e:      # a failed leg must not take the headline line with it
         return {"error": repr(e)[:400]}
+
+
+DUMP_CAP = 7_500_000        # values per dumped array: 30 MB of float32, so tokens + pixels stay under 64 MB
+
+
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (tokens < 2^24 are exact) — all of it, or, past DUMP_CAP values, the values at DUMP_CAP flat
+    indices drawn by a CPU generator seeded with `seed` and sorted (1-D).  The indices depend only on the shape, so two runs with the same arguments (the inputs
+    and weights are seeded) compare value for value, whichever build of the library made them."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = torch.randint(0, t.numel(), (DUMP_CAP,), generator=torch.Generator().manual_seed(seed)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -462,27 +490,31 @@ def main():
         all_toks = gather_tokens(dist, toks)                # [G, n_new] on every rank, global image order
         torch.cuda.synchronize(); t_gather = time.perf_counter() - t_g0
         assert all_toks.shape[0] == G
-    assert bool(torch.isfinite(px).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"tokens": toks, "pixels": px})
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     parity = {}
-    if twin > 0:
-        parity["twin_rows_equal"] = bool(torch.equal(toks[0], toks[twin]))
-        parity["twin_pixels_max_abs_diff"] = float((px[0] - px[twin]).abs().max())
-        assert parity["twin_rows_equal"], "identical inputs in two rows of the batch produced different tokens"
-    gpath = os.path.join(ROOT, "tests", "golden", "xl_canny_512_cfg1.npz")
-    if (rank == 0 and args.model == "xl" and (Hh, Ww) == (512, 512) and args.cfg_scale <= 1.0 and args.adapter_size == "small"
-            and args.condition_type == "canny" and not args.weights_fp8 and not args.kv_fp8 and not args.sample_logits and os.path.exists(gpath)):
-        # local image 0 of rank 0 is the input of the committed golden (synth seed 1234): the reference's fp32 greedy tokens.
-        # The bf16 fast mode free-runs, so it follows them until the first near-tie and is graded teacher-forced in
-        # tests/test_bench_shapes_gpu.py; here the common prefix and overall agreement are reported and sanity-bounded.
-        import numpy as np
-        gold = np.load(gpath)["tokens"][0]
-        mine = toks[0].cpu().numpy()
-        neq = np.nonzero(mine != gold)[0]
-        parity["golden_prefix_tokens"] = int(neq[0]) if len(neq) else int(len(gold))
-        parity["golden_token_agreement"] = float((mine == gold).mean())
-        assert parity["golden_prefix_tokens"] >= 2, parity
-        if args.precision == "fp32":       # exact mode: the reference's greedy tokens, all of them, whatever the batch (batch-invariant kernels)
-            assert parity["golden_token_agreement"] == 1.0, parity
+    if args.full:
+        assert bool(torch.isfinite(px).all())
+        if twin > 0:
+            parity["twin_rows_equal"] = bool(torch.equal(toks[0], toks[twin]))
+            parity["twin_pixels_max_abs_diff"] = float((px[0] - px[twin]).abs().max())
+            assert parity["twin_rows_equal"], "identical inputs in two rows of the batch produced different tokens"
+        gpath = os.path.join(ROOT, "tests", "golden", "xl_canny_512_cfg1.npz")
+        if (rank == 0 and args.model == "xl" and (Hh, Ww) == (512, 512) and args.cfg_scale <= 1.0 and args.adapter_size == "small"
+                and args.condition_type == "canny" and not args.weights_fp8 and not args.kv_fp8 and not args.sample_logits and os.path.exists(gpath)):
+            # local image 0 of rank 0 is the input of the committed golden (synth seed 1234): the reference's fp32 greedy tokens.
+            # The bf16 fast mode free-runs, so it follows them until the first near-tie and is graded teacher-forced in
+            # tests/test_bench_shapes_gpu.py; here the common prefix and overall agreement are reported and sanity-bounded.
+            import numpy as np
+            gold = np.load(gpath)["tokens"][0]
+            mine = toks[0].cpu().numpy()
+            neq = np.nonzero(mine != gold)[0]
+            parity["golden_prefix_tokens"] = int(neq[0]) if len(neq) else int(len(gold))
+            parity["golden_token_agreement"] = float((mine == gold).mean())
+            assert parity["golden_prefix_tokens"] >= 2, parity
+            if args.precision == "fp32":       # exact mode: the reference's greedy tokens, all of them, whatever the batch (batch-invariant kernels)
+                assert parity["golden_token_agreement"] == 1.0, parity
 
     # HBM traffic of one decode step (read + write) is taken from the committed PMC summary of the SAME configuration
     # (profiles/pmc_decode_step.json, written by tools/pmc_decode.py from `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE`
@@ -547,29 +579,30 @@ def main():
             pass
         # VQ decoder cost in both arithmetics (the reference keeps vq_model in fp32, sample_t2i.py:43-47; both bench modes decode pixels in bf16 by default):
         # HIP-event time of car_vq_decode on a slice of this step's tokens, outside the timed region
-        try:
-            nb = min(args.batch, 48)
-            vq_ms = {}
-            for prec_ in ("bf16", "fp32"):
-                if prec_ != args.vq_precision and vsd is None:      # this rank imported packed images: no state dict at hand for a second decoder context
-                    continue
-                ve = vq_eng if prec_ == args.vq_precision else Engine(cfg, prec_, device=dev)
-                if ve is not vq_eng:
-                    ve.load_state_dict(vsd, finalize=True)
-                ve.vq_decode(toks[:nb], gh, gw); torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); ve.vq_decode(toks[:nb], gh, gw); e1.record(); torch.cuda.synchronize()
-                vq_ms[prec_] = e0.elapsed_time(e1) / nb
-                if ve is not vq_eng:
-                    ve.close()
-            out["config"]["vq_ms_per_image"] = {**vq_ms, "images": nb, "in_timed_region": args.vq_precision}
-        except Exception as e:
-            out["config"]["vq_ms_per_image"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            try:
+                nb = min(args.batch, 48)
+                vq_ms = {}
+                for prec_ in ("bf16", "fp32"):
+                    if prec_ != args.vq_precision and vsd is None:      # this rank imported packed images: no state dict at hand for a second decoder context
+                        continue
+                    ve = vq_eng if prec_ == args.vq_precision else Engine(cfg, prec_, device=dev)
+                    if ve is not vq_eng:
+                        ve.load_state_dict(vsd, finalize=True)
+                    ve.vq_decode(toks[:nb], gh, gw); torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); ve.vq_decode(toks[:nb], gh, gw); e1.record(); torch.cuda.synchronize()
+                    vq_ms[prec_] = e0.elapsed_time(e1) / nb
+                    if ve is not vq_eng:
+                        ve.close()
+                out["config"]["vq_ms_per_image"] = {**vq_ms, "images": nb, "in_timed_region": args.vq_precision}
+            except Exception as e:
+                out["config"]["vq_ms_per_image"] = {"error": repr(e)[:200]}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, gsd, vsd, Hh, Ww, args.cpu_tokens)
         headline = (args.config == 0 and args.precision == "bf16" and args.model == "xl" and (Hh, Ww) == (512, 512) and not args.weights_fp8 and not args.kv_fp8
                     and not args.sample_logits and args.cfg_scale <= 1.0)
-        if world == 1 and not args.no_variants and ((headline and (args.exact_leg_steps > 0 or legs)) or (args.config == 5 and args.fp8_mfma)):
+        if world == 1 and args.full and not args.no_variants and ((headline and (args.exact_leg_steps > 0 or legs)) or (args.config == 5 and args.fp8_mfma)):
             eng.close(); vq_eng.close(); del img, emb, mask, toks, px
             torch.cuda.empty_cache()
             if headline and args.exact_leg_steps > 0:

@@ -88,37 +88,25 @@ def test_dropin_modules_import_and_factories_build_without_gpu():
 
 def test_decode_code_argument_forms_fail_as_in_the_reference():
     """VQModel.decode_code(shape=None) and (channel_first=False) are not usable in the reference either (vq_model.py:53-56,262-277: a 2-D gather, resp.
-    a [B,h,w,C] tensor, reaches the NCHW post_quant_conv): the drop-in raises the same exception type with the same reason; when the reference
-    tree is present (build container) its own behaviour is checked beside it."""
-    import sys
+    a [B,h,w,C] tensor, reaches the NCHW post_quant_conv): the drop-in raises the same exception type with the same reason.  What the reference
+    itself raised for each form, and its output shape for the form the path uses, are recorded in tests/golden/reference_vq_decode_code_forms.json:
+    the drop-in's message starts with the reference's."""
+    import json
     import torch
     from controlar_amd import models as M
     vq = M.VQ_models["VQ-16"](codebook_size=16384, codebook_embed_dim=8)
     code = torch.zeros(2, 16, dtype=torch.int64)
-    with pytest.raises(RuntimeError, match="conv2d"):
-        vq.decode_code(code.reshape(-1))                               # shape=None, flat codes: a 2-D gather
-    with pytest.raises(RuntimeError, match="channels"):
-        vq.decode_code(code)                                           # shape=None, [B, N] codes: [B, N, C] taken for one unbatched image
-    with pytest.raises(RuntimeError, match="channels"):
-        vq.decode_code(code, (2, 4, 4, 8), channel_first=False)        # [B, h, w, C] with h != C
-    ref_root = "/root/reference"
-    if os.path.isdir(ref_root):
-        sys.path.insert(0, ref_root)
-        try:
-            from tokenizer.tokenizer_image.vq_model import VQ_models as RefVQ
-        except Exception:
-            return
-        finally:
-            sys.path.remove(ref_root)
-        ref = RefVQ["VQ-16"](codebook_size=64, codebook_embed_dim=8).eval()
-        with torch.no_grad():
-            with pytest.raises(RuntimeError, match="conv2d"):
-                ref.decode_code(code.reshape(-1))
-            with pytest.raises(RuntimeError, match="channels"):
-                ref.decode_code(code)
-            with pytest.raises(RuntimeError, match="channels"):
-                ref.decode_code(code, (2, 4, 4, 8), channel_first=False)
-            assert tuple(ref.decode_code(code, (2, 8, 4, 4)).shape) == (2, 3, 64, 64)     # the one form the path uses
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_vq_decode_code_forms.json")))
+    forms = {"flat_codes_shape_none": ("conv2d", lambda: vq.decode_code(code.reshape(-1))),           # shape=None, flat codes: a 2-D gather
+             "batched_codes_shape_none": ("channels", lambda: vq.decode_code(code)),                 # shape=None, [B, N] codes: [B, N, C] taken for one unbatched image
+             "channel_last_shape_2x4x4x8": ("channels", lambda: vq.decode_code(code, (2, 4, 4, 8), channel_first=False))}     # [B, h, w, C] with h != C
+    for name, (reason, call) in forms.items():
+        assert ref[name]["exception"] == "RuntimeError" and reason in ref[name]["message"]
+        with pytest.raises(RuntimeError, match=reason) as ei:
+            call()
+        assert str(ei.value).startswith(ref[name]["message"]), (name, str(ei.value))
+    up = 2 ** (len(vq.vq.ch_mult) - 1)                                 # the decoder's upsampling: [B, C, h, w] latents -> [B, 3, up*h, up*w] pixels
+    assert ref["channel_first_shape_2x8x4x4"]["output_shape"] == [2, 3, 4 * up, 4 * up]     # the one form the path uses
 
 
 def test_header_is_valid_c99_and_example_compiles():

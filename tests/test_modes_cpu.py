@@ -65,14 +65,35 @@ def test_bench_config_presets(monkeypatch):
     a = args("--config", "4"); assert (a.cfg_scale, a.batch, a.image_h, a.image_w) == (4.0, 1, 768, 512)
     a = args("--config", "5"); assert (a.batch, a.fp8_mfma, a.weights_fp8, a.adapter_size) == (8, True, True, "base")        # BASELINE configs[4] as named: W8A8 on the fp8 MFMA
     a = args("--config", "5", "--fp8-weight-only"); assert (a.batch, a.fp8_mfma, a.weights_fp8) == (8, False, True)          # the weight-only variant (reported beside it)
-    assert args().exact_leg_steps == 3 and not args().no_variants                                                            # the default run times the bit-identical mode too
-    assert bench.config_legs(args(), 1) == [2, 3, 5, 4, 1] and bench.config_legs(args(), 8) == []                          # ... on one GPU only: at N > 1 no rank spawns child legs
-    assert bench.config_legs(args("--config", "2"), 1) == [] and bench.config_legs(args("--no-variants"), 1) == [] and bench.config_legs(args("--precision", "fp32"), 1) == []
+    assert args().exact_leg_steps == 3 and not args().no_variants and args("--full").full                                 # the --full run times the bit-identical mode too
+    assert bench.config_legs(args("--full"), 1) == [2, 3, 5, 4, 1] and bench.config_legs(args("--full"), 8) == []          # ... on one GPU only: at N > 1 no rank spawns child legs
+    assert not args().full and bench.config_legs(args(), 1) == []                                                           # a plain run times the headline and nothing else
+    assert bench.config_legs(args("--full", "--config", "2"), 1) == [] and bench.config_legs(args("--full", "--no-variants"), 1) == [] and bench.config_legs(args("--full", "--precision", "fp32"), 1) == []
     assert args().config_legs == "2,3,5,4,1" and not args().pack_cache                                                       # ... and every other BASELINE config (round 6: the `configs` block)
     a = args("--gpus", "8", "--steps", "20", "--warmup", "5"); assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
     a = args("--precision", "fp32"); assert (a.batch, a.vq_precision) == (384, "bf16")          # the tokens-exact configuration: fp32 KV of 384 sequences = 162 GB, bf16 pixels
     a = args("--precision", "fp32", "--vq-precision", "fp32", "--batch", "192"); assert (a.batch, a.vq_precision) == (192, "fp32")
     assert args().vq_precision == "bf16"
+
+
+def test_bench_dump_outputs_are_float32_seeded_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: the last timed step's arrays as float32 .npy; a larger array is cut to a sample at seeded flat indices — the same indices
+    on every run — and two full-size samples stay under 64 MB."""
+    import importlib
+    import os
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    assert 2 * bench.DUMP_CAP * 4 + 2 * 4096 <= 64e6
+    monkeypatch.setattr(bench, "DUMP_CAP", 1000)
+    toks = torch.arange(96, dtype=torch.int32).reshape(12, 8) * 170         # codebook indices up to 16150
+    px = torch.randn(4, 3, 16, 16, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"tokens": toks, "pixels": px})
+    t, p, p2 = (np.load(tmp_path / d / f) for d, f in (("a", "tokens.npy"), ("a", "pixels.npy"), ("b", "pixels.npy")))
+    assert t.dtype == np.float32 and t.shape == (12, 8) and np.array_equal(t, toks.numpy())
+    assert p.dtype == np.float32 and p.shape == (1000,) and np.array_equal(p, p2)
+    assert np.isin(p, px.float().numpy()).all() and len(np.unique(p)) > 500
 
 
 def test_bench_refuses_library_switches(monkeypatch):

@@ -9,7 +9,7 @@ bash tools/probe.sh mid-chain $O/r06_final/mid > $O/r06_final/mid_chain.log 2>&1
 bash tools/probe.sh kbench $O/r06_final/kbench > $O/r06_final/kbench.log 2>&1; tail -1 $O/r06_final/kbench.log
 bash tools/profile_round.sh r06 > $O/r06_final/profile_round.log 2>&1
 cp $O/pmc_decode_step.json profiles/pmc_decode_step.json 2>/dev/null; cp $O/pmc_decode_step_fp32.json profiles/pmc_decode_step_fp32.json 2>/dev/null
-( time python bench.py --steps 3 --warmup 1 > $O/r06_final/r06_bench_b768.json 2> $O/r06_final/bench.err ) 2>> $O/r06_final/bench.err
+( time python bench.py --full --steps 3 --warmup 1 > $O/r06_final/r06_bench_b768.json 2> $O/r06_final/bench.err ) 2>> $O/r06_final/bench.err
 tail -4 $O/r06_final/bench.err
 cp profiles/pmc_decode_step.json $O/r06_final/ 2>/dev/null; cp profiles/pmc_decode_step_fp32.json $O/r06_final/ 2>/dev/null
 cat $O/r06_final/small_chain.log $O/r06_final/mid_chain.log | grep instrumented
