@@ -1,5 +1,6 @@
 """Condition extractors of the path's front end.  ``CannyDetector`` keeps the call shape of the reference's
-``condition/canny.py:6-14`` (array or tensor (H, W, 3) in, array (H, W) out) and runs ``car_canny`` on the GPU."""
+``condition/canny.py:6-14`` (array or tensor (H, W, 3) in, array (H, W) out) and runs ``car_canny`` on the GPU.  ``LineArt`` keeps the call shape of
+``condition/lineart.py:26-86`` (tensor (B, 3, H, W) in, tensor (B, 1, Ho, Wo) in 0..1 out) and runs ``car_lineart``."""
 from __future__ import annotations
 
 import numpy as np
@@ -19,3 +20,31 @@ class CannyDetector:
             img = img.cpu().detach().numpy().astype(np.uint8)
         x = torch.from_numpy(np.ascontiguousarray(np.asarray(img, dtype=np.uint8)))
         return self._eng.canny(x, low_threshold, high_threshold).cpu().numpy()
+
+
+class LineArt:
+    """Drop-in for the reference's ``LineArt()`` module (default constructor: 3 residual blocks, sigmoid) as the sampling scripts use it
+    (sample_t2i.py:110-113: construct, load_state_dict, .to(device); :129-132: call).  The weights live in a context of their own."""
+
+    def __init__(self, input_nc=3, output_nc=1, n_residual_blocks=3, sigmoid=True, precision="bf16", device=None):
+        if (input_nc, output_nc, n_residual_blocks, sigmoid) != (3, 1, 3, True):
+            raise NotImplementedError("car_lineart implements the reference's default LineArt(3, 1, 3, sigmoid=True)")
+        self.precision = precision
+        self._eng = Engine(tiny_t2i(), precision, device=device)     # the config only shapes the GPT / VQ side, which this context does not hold
+
+    def load_state_dict(self, sd, strict=True):
+        self._eng.load_lineart(sd, finalize=True)
+        return self
+
+    def to(self, device=None, *args, **kwargs):
+        return self
+
+    def eval(self):
+        return self
+
+    def forward(self, x, cond=None):
+        """input: tensor (B,C,H,W)   output: tensor (B,1,H,W) 0~1   (condition/lineart.py:74-86)"""
+        return self._eng.lineart(x).to(x.device)
+
+    def __call__(self, x, cond=None):
+        return self.forward(x, cond)

@@ -138,6 +138,16 @@ static std::string canon_name(const std::string& in) {
     return s;
 }
 
+// the 24 tensors of LineArt(n_residual_blocks = 3).state_dict(), under the "lineart." prefix of the C ABI
+static std::vector<std::string> lineart_tensor_names() {
+    std::vector<std::string> v;
+    std::vector<std::string> mods = {"model0.1", "model1.0", "model1.3"};
+    for (int r = 0; r < 3; ++r) for (const char* s : {".conv_block.1", ".conv_block.5"}) mods.push_back("model2." + std::to_string(r) + s);
+    for (const char* s : {"model3.0", "model3.3", "model4.1"}) mods.push_back(s);
+    for (auto& m : mods) { v.push_back("lineart." + m + ".weight"); v.push_back("lineart." + m + ".bias"); }
+    return v;
+}
+
 extern "C" int car_load_tensor(car_ctx* c, const char* cname, const void* ptr, const int64_t* shape, int32_t ndim, int32_t dtype) {
     if (!c || !cname || !ptr || (ndim > 0 && !shape)) { if (c) c->err = "car_load_tensor: null argument"; return -1; }
     if (dtype != CAR_DT_F32 && dtype != CAR_DT_BF16) FAIL(c, "car_load_tensor(%s): dtype must be F32 or BF16", cname);
@@ -184,6 +194,46 @@ extern "C" int car_load_tensor(car_ctx* c, const char* cname, const void* ptr, c
     const car_config& g = c->cfg;
     c->finalized = false;
     // ---- name-specific packing
+    if (starts_with(name, "lineart.")) {
+        // LineArt extractor (condition/lineart.py:26-86; car_lineart).  Conv weights become implicit-GEMM images [Cout][taps*Cin] (k = tap*Cin + ci, K padded to
+        // the 32-wide k step) in the context's element type; a ConvTranspose2d weight [Cin,Cout,3,3] becomes its four output-parity phase images, concatenated
+        // in the order (py,px) = (0,0) (0,1) (1,0) (1,1) with 1, 2, 2 and 4 taps: parity 0 takes kernel index 1 at input offset 0, parity 1 takes index 2 at
+        // offset 0 and index 0 at offset +1.  Biases stay fp32 (only model4's is applied: a bias in front of an InstanceNorm cancels).
+        const std::string key = name.substr(8);
+        int li = -1;
+        const std::vector<std::string> names = lineart_tensor_names();
+        for (size_t i = 0; i < names.size(); ++i) if (names[i] == name) li = (int)i;
+        if (li < 0) FAIL(c, "%s: not a tensor of the LineArt generator (n_residual_blocks = 3)", cname);
+        if (ends_with(name, ".bias")) {
+            if (ndim != 1) FAIL(c, "%s: unexpected shape", cname);
+            return upload(c, name, h, shp, true);
+        }
+        if (ndim != 4 || shp[2] != shp[3]) FAIL(c, "%s: unexpected shape", cname);
+        const int ks = (int)shp[2];
+        if (starts_with(key, "model3.")) {
+            const int Ci = (int)shp[0], Co = (int)shp[1];
+            if (ks != 3 || (key == "model3.0.weight" ? (Ci != 256 || Co != 128) : (Ci != 128 || Co != 64))) FAIL(c, "%s: unexpected shape", cname);
+            std::vector<float> pk((size_t)9 * Ci * Co);
+            size_t o = 0;
+            for (int ph = 0; ph < 4; ++ph) {
+                const int py = ph >> 1, px = ph & 1, ny = py ? 2 : 1, nx = px ? 2 : 1;
+                for (int co = 0; co < Co; ++co) for (int a = 0; a < ny; ++a) for (int b = 0; b < nx; ++b) {
+                    const int ky = py ? (a == 0 ? 2 : 0) : 1, kx = px ? (b == 0 ? 2 : 0) : 1;
+                    for (int ci = 0; ci < Ci; ++ci) pk[o++] = h[(((size_t)ci * Co + co) * 3 + ky) * 3 + kx];
+                }
+            }
+            return upload(c, name, pk, {9, Co, Ci});
+        }
+        const int Co = (int)shp[0], Ci = (int)shp[1], K = ks * ks * Ci, Kp = (int)rup((size_t)K, 32);
+        int eCo = 256, eCi = 256, eks = 3;
+        if (key == "model0.1.weight") { eCo = 64; eCi = 3; eks = 7; } else if (key == "model1.0.weight") { eCo = 128; eCi = 64; }
+        else if (key == "model1.3.weight") { eCo = 256; eCi = 128; } else if (key == "model4.1.weight") { eCo = 1; eCi = 64; eks = 7; }
+        if (Co != eCo || Ci != eCi || ks != eks) FAIL(c, "%s: expected [%d,%d,%d,%d]", cname, eCo, eCi, eks, eks);
+        std::vector<float> pk((size_t)Co * Kp, 0.f);
+        for (int o = 0; o < Co; ++o) for (int ci = 0; ci < Ci; ++ci) for (int t = 0; t < ks * ks; ++t)
+            pk[(size_t)o * Kp + (size_t)t * Ci + ci] = h[((size_t)o * Ci + ci) * ks * ks + t];
+        return upload(c, name, pk, {Co, Kp});
+    }
     if (starts_with(name, "t5.")) {
         // caption encoder (car_t5_encode).  A full T5 state dict may be offered: the decoder half, lm_head and the tied alias are skipped.
         if (!c->has_t5) FAIL(c, "%s: call car_t5_configure before loading t5.* tensors", cname);
@@ -302,7 +352,12 @@ extern "C" int car_finalize_weights(car_ctx* c) {
     int nmiss = 0;
     // a context may serve only decode_code (VQ weights alone) — the reference keeps GPT and VQ as separate modules
     const bool have_t5 = c->has_t5 && Wp(c, "t5.shared.weight");
-    const bool vq_only = (Wp(c, "quantize.embedding.weight") || have_t5) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
+    // the LineArt extractor is optional as a group, complete once one of its tensors has arrived; a context may hold it alone
+    const std::vector<std::string> la_names = lineart_tensor_names();
+    bool have_la = false;
+    for (auto& r : la_names) if (Wp(c, r)) have_la = true;
+    if (have_la) for (auto& r : la_names) if (!Wp(c, r)) { if (nmiss < 6) missing += r + " "; ++nmiss; }
+    const bool vq_only = (Wp(c, "quantize.embedding.weight") || have_t5 || have_la) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
     c->has_gpt = !vq_only;
     if (have_t5) {       // the caption encoder is optional as a group, complete if present
         std::vector<std::string> tr = {"t5.encoder.final_layer_norm.weight"};

@@ -44,3 +44,16 @@ struct FlashP {
     const float* bias;                // [H][Tq][Tk]
 };
 
+// ------------------------------------------------------------------ LineArt extractor (lineart.hip; condition/lineart.py:26-86)
+// One implicit-GEMM convolution launch: GEMM rows = the Hg x Wg grid of ONE image (blockIdx.z), row (gy, gx) reads input pixel
+// (gy*stride + dy[t], gx*stride + dx[t]) for tap t — reflected at the border (reflect = 1) or zero outside it — and lands at output pixel
+// (gy*os + py, gx*os + px): os = 2 with a parity (py, px) is one phase of a transposed convolution.  k = t*Cin + ci, weights [N][Kp].
+struct LaConvP {
+    const void* in; const void* w; float* raw; float* part; int* cnt;
+    long in_img, raw_img;             // per-image element strides of `in` / `raw`
+    int Hi, Wi, Cin, N, K, Kp;
+    int Hg, Wg, Hout, Wout;
+    int stride, os, py, px, reflect, ntaps;
+    int tile0, tiles_img;             // first InstanceNorm partial slot of this launch; partial slots per image
+    signed char dy[49], dx[49];
+};

@@ -253,6 +253,29 @@ class Engine:
         edges = edges[0] if single else edges
         return (edges, ctrl) if want_control else edges
 
+    def load_lineart(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
+        """LineArt().state_dict() names (condition/lineart.py:26-72: model0.1.weight ... model4.1.bias); the C ABI namespaces them under 'lineart.'."""
+        self.load_state_dict({"lineart." + k: v for k, v in sd.items()}, finalize=finalize)
+
+    @staticmethod
+    def lineart_output_size(H: int, W: int):
+        """The network's own output size: two stride-2 convs (floor((n-1)/2)+1 each) followed by two 2x transposed convs."""
+        down = lambda n: ((n - 1) // 2 + 1 - 1) // 2 + 1
+        return 4 * down(H), 4 * down(W)
+
+    def lineart(self, img: torch.Tensor, want_control: bool = False):
+        """LineArt.forward (condition/lineart.py:74-86) on the GPU.  img [B,3,H,W], raw 0..255 values -> fp32 [B,1,Ho,Wo] in (0,1); with want_control
+        also the control tensor [B,3,Ho,Wo] = 1 - 2*out in the context's element type (sample_t2i.py:131-132,141)."""
+        assert img.dim() == 4 and img.shape[1] == 3, "expected an image batch [B, 3, H, W]"
+        x = img.to(device=self.device, dtype=torch.float32).contiguous()
+        B, _, H, W = x.shape
+        Ho, Wo = self.lineart_output_size(H, W)
+        out = torch.empty(B, 1, max(Ho, 0), max(Wo, 0), dtype=torch.float32, device=self.device)
+        ctrl = torch.empty(B, 3, max(Ho, 0), max(Wo, 0), dtype=self.dtype, device=self.device) if want_control else None
+        self._check(self.lib.car_lineart(self._h, C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()),
+                                         C.c_void_p(ctrl.data_ptr() if ctrl is not None else 0), C.c_void_p(_stream_ptr())), "car_lineart")
+        return (out, ctrl) if want_control else out
+
     # ------------------------------------------------------------------ caption encoder (language/t5.py)
     def t5_configure(self, t5cfg):
         tc = L.CarT5Config()

@@ -348,3 +348,30 @@ def t5_tokens(batch: int, cfg: T5Config, seed: int = 4321, lengths=None):
         ids[b, L - 1] = 1
         mask[b, :L] = 1
     return ids, mask
+
+
+def lineart_state_dict(seed: int = 11) -> Dict[str, torch.Tensor]:
+    """LineArt().state_dict() names and shapes (reference condition/lineart.py:26-72, n_residual_blocks = 3): 24 tensors.  The stock initialisation gives
+    an output of about 0.5 everywhere, which pins nothing; here every weight is N(0, 1/fan_in) (a transposed conv sees 9/4 taps per output on average),
+    biases are N(0, 0.1^2), and the last conv is scaled x3 so that the sigmoid output spreads over (0, 1)."""
+    r = _Rng(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def conv(name, co, ci, k, gain=1.0):
+        sd[name + ".weight"] = r.normal(co, ci, k, k, std=gain * (ci * k * k) ** -0.5)
+        sd[name + ".bias"] = r.normal(co, std=0.1)
+
+    def convt(name, ci, co):
+        sd[name + ".weight"] = r.normal(ci, co, 3, 3, std=(ci * 9 / 4) ** -0.5)
+        sd[name + ".bias"] = r.normal(co, std=0.1)
+
+    conv("model0.1", 64, 3, 7)
+    conv("model1.0", 128, 64, 3)
+    conv("model1.3", 256, 128, 3)
+    for i in range(3):
+        conv(f"model2.{i}.conv_block.1", 256, 256, 3)
+        conv(f"model2.{i}.conv_block.5", 256, 256, 3)
+    convt("model3.0", 256, 128)
+    convt("model3.3", 128, 64)
+    conv("model4.1", 1, 64, 7, gain=3.0)
+    return sd

@@ -165,6 +165,19 @@ int car_canny(car_ctx* ctx, const uint8_t* img_hwc, int32_t B, int32_t H, int32_
               uint8_t* edges_out, void* control_out, void* stream);
 
 /*
+ * LineArt control extraction — replaces LineArt.forward (condition/lineart.py:26-86, default constructor: 3 residual blocks, sigmoid; callers
+ * sample_t2i.py:110-113,129-132, sample_t2i_MR.py, autoregressive/test/test_t2i.py:177).  img_nchw: fp32 [B,3,H,W] (device), raw 0..255 values as the
+ * reference receives them.  out: fp32 [B,1,Ho,Wo] in (0,1) or NULL; control_out: [B,3,Ho,Wo] in the context's element type, = 1 - 2*out replicated over
+ * 3 channels (1 - y, *255, 2*(x/255 - 0.5) of sample_t2i.py:131-132,141), ready for car_encode_control, or NULL.  The output size is the network's own:
+ * Ho = 4*ceil(ceil(H/2)/2), likewise Wo (30 x 44 in -> 32 x 44 out).  H or W below 5 is an error (the reference raises there).  The context's mode sets
+ * the arithmetic: bf16 operands / fp32 accumulation and InstanceNorm statistics / bf16 activations, or fp32 throughout.  Weights: the 24 tensors of
+ * LineArt().state_dict() through car_load_tensor under "lineart." + key (model0.1.weight ... model4.1.bias), then car_finalize_weights; a context may
+ * hold them alone or next to a GPT / VQ / T5 model.  Deterministic (no atomics), batch-invariant per image, no host synchronisation.
+ */
+int car_lineart(car_ctx* ctx, const float* img_nchw, int32_t B, int32_t H, int32_t W,
+                float* out, void* control_out, void* stream);
+
+/*
  * Caption encoder — replaces T5Embedder.get_text_embeddings' model call (language/t5.py:185-201:
  * self.model(input_ids, attention_mask)['last_hidden_state'], HF T5EncoderModel built at language/t5.py:58-79; callers
  * sample_t2i.py:99-118, demo/model.py).  The tokenizer stays on the host side of the boundary (sentencepiece, CPU string work).
