@@ -91,73 +91,8 @@ __device__ inline void car_pf_helper(const void* p0, unsigned b0, const void* p1
     asm volatile("" ::"v"(acc));          // keeps the loads alive
 }
 
-// ---------------------------------------------------------------------------------------------- early launch (decode2_params.h CAR_HS_FIELDS)
-// Compiled in only with -DCAR_EARLY_LAUNCH (experiments/lat_probe): in the product build HS_FRESH / HS_WT are the constant false and the loads / stores below are plain.
-#ifdef CAR_EARLY_LAUNCH
-#define HS_FRESH(p) ((p).dep != nullptr)
-#define HS_WT(p) ((p).done != nullptr)
-#define HS_WAIT(p) car_hs_wait((p).dep, (p).dep_n, (p).hs_err)
-#define HS_ARRIVE(p) car_hs_arrive((p).done)
-#else
-#define HS_FRESH(p) false
-#define HS_WT(p) false
-#define HS_WAIT(p) do { } while (0)
-#define HS_ARRIVE(p) do { } while (0)
-#endif
-typedef unsigned long long u64_t;
 typedef __attribute__((address_space(1))) const void car_gptr_t;
 typedef __attribute__((address_space(3))) void car_lptr_t;
-__device__ __forceinline__ u64_t car_ld8_agent(const void* q) { return __hip_atomic_load((const u64_t*)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// 16 bytes the predecessor kernel wrote (fresh != 0: two 8-byte agent-scope loads) or anything older (a plain 16-byte load)
-__device__ __forceinline__ u32x4 car_ld16(const void* q, bool fresh) {
-    if (!fresh) return *(const u32x4*)q;
-    const u64_t a = car_ld8_agent(q), b = car_ld8_agent((const char*)q + 8);
-    u32x4 r; r[0] = (unsigned)a; r[1] = (unsigned)(a >> 32); r[2] = (unsigned)b; r[3] = (unsigned)(b >> 32);
-    return r;
-}
-__device__ __forceinline__ uint2 car_ld8(const void* q, bool fresh) {
-    if (!fresh) return *(const uint2*)q;
-    const u64_t a = car_ld8_agent(q); uint2 r; r.x = (unsigned)a; r.y = (unsigned)(a >> 32); return r;
-}
-// stores of what the SUCCESSOR kernel reads: write-through agent-scope atomics when it may already be running (wt), plain stores otherwise
-__device__ __forceinline__ void car_st8(void* q, uint2 v, bool wt) {
-    if (wt) __hip_atomic_store((u64_t*)q, ((u64_t)v.y << 32) | v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(uint2*)q = v;
-}
-__device__ __forceinline__ void car_st4(void* q, unsigned v, bool wt) {
-    if (wt) __hip_atomic_store((unsigned*)q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(unsigned*)q = v;
-}
-__device__ __forceinline__ void car_st2(void* q, bf16_t v, bool wt) {
-    if (wt) __hip_atomic_store((unsigned short*)q, (unsigned short)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(bf16_t*)q = v;
-}
-__device__ __forceinline__ void car_st1(void* q, unsigned char v, bool wt) {
-    if (wt) __hip_atomic_store((unsigned char*)q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(unsigned char*)q = v;
-}
-// Whole workgroup: returns once every workgroup of the predecessor has arrived (or the schedule is declared dead).  One wave polls: lanes 0-7 the eight shard
-// counters, lane 8 the sticky error word.  Bounded: ~2^17 polls (~0.1 s) then the error word is set and every later wait in the step returns at once.
-__device__ __forceinline__ void car_hs_wait(const unsigned* dep, int dep_n, unsigned* err) {
-    if (!dep) return;
-    if (threadIdx.x < 64) {
-        const int lane = (int)threadIdx.x;
-        const unsigned need = lane < 8 ? (unsigned)((dep_n + 7 - lane) >> 3) : 0u;
-        for (unsigned spins = 0;; ++spins) {
-            unsigned v = 0;
-            if (lane < 8) v = __hip_atomic_load(dep + lane * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else if (lane == 8) v = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool ok = lane < 8 ? v >= need : true, dead = lane == 8 && v != 0u;
-            if (__all(ok) || __any(dead)) break;
-            if (spins > (1u << 17)) { if (lane == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-            __builtin_amdgcn_s_sleep(2);
-        }
-    }
-    __syncthreads();
-}
-// Whole workgroup, after its last store: every wave drains, the workgroup meets, one lane arrives on its shard.
-__device__ __forceinline__ void car_hs_arrive(unsigned* done) {
-    if (!done) return;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(done + (blockIdx.x & 7) * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // OCP e4m3fn has no infinity: values beyond +-448 must saturate BEFORE the conversion (the oracle's kv_fp8 model and include/controlar_hip.h say
 // clamp(-448, 448); an unclamped outlier would be stored as NaN and poison every later attention step of the sequence, since P * NaN = NaN even at P = 0)
@@ -245,9 +180,7 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
     const bf16_t* hrow[J]; bool hok[J]; float rstd[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) { const int m = (mb0 + j) * 16 + (lane & 15); hok[j] = NORM == 2 && m < p.M; hrow[j] = NORM == 2 ? p.nh_in + (long)(hok[j] ? m : 0) * p.K + (lane >> 4) * 8 : nullptr; rstd[j] = 0.f; }
-    const bool hs_fresh = HS_FRESH(p);               // early launch: X / the residual rows / their statistics come from a kernel that may still be running
-    const bool hs_wt = HS_WT(p);                     // ... and this kernel's outputs are read by one that may already be
-    // a stage's operands in two halves: what does not depend on the predecessor (weights, norm weight) and what does (X)
+    // a stage's operands in two halves: weights + norm weight, and X (only load() calls them; written as one lambda the kernels compile to different code)
     auto loadW = [&](u32x4 (&w)[I], u32x4 (&nwf)[NORM == 2 ? XPU : 1], int ku) {
 #pragma unroll
         for (int i = 0; i < I; ++i) {
@@ -264,12 +197,12 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
 #pragma unroll
             for (int j = 0; j < J; ++j)
 #pragma unroll
-                for (int u = 0; u < XPU; ++u) { x[j * XPU + u] = zw; if (j < jn) x[j * XPU + u] = car_ld16(xp + ((long)j * nkb + ku * XPU + u) * 64, hs_fresh); }      // (round 6 tried masking the lanes of rows >= M: the exec juggling cost more issue time than the narrower loads saved — wo 0.52 -> 0.86 us, w2 1.16 -> 1.42)
+                for (int u = 0; u < XPU; ++u) { x[j * XPU + u] = zw; if (j < jn) x[j * XPU + u] = xp[((long)j * nkb + ku * XPU + u) * 64]; }      // (round 6 tried masking the lanes of rows >= M: the exec juggling cost more issue time than the narrower loads saved — wo 0.52 -> 0.86 us, w2 1.16 -> 1.42)
         } else if (NORM == 2) {
 #pragma unroll
             for (int j = 0; j < J; ++j)
 #pragma unroll
-                for (int u = 0; u < XPU; ++u) { x[j * XPU + u] = zw; if (hok[j]) x[j * XPU + u] = car_ld16(hrow[j] + (ku * XPU + u) * 32, hs_fresh); }
+                for (int u = 0; u < XPU; ++u) { x[j * XPU + u] = zw; if (hok[j]) x[j * XPU + u] = *(const u32x4*)(hrow[j] + (ku * XPU + u) * 32); }
         }
     };
     auto load = [&](u32x4 (&w)[I], u32x4 (&x)[J * XPU], u32x4 (&nwf)[NORM == 2 ? XPU : 1], int ku) { loadW(w, nwf, ku); loadX(x, ku); };
@@ -346,7 +279,7 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
     // the prologue measured 5.2-6.6 us of an 8 us kernel (experiments/lat_probe, profiles/r04_lat_probe_before_rows2.txt); issued first, it costs one L2 round trip.
     uint2 nh[8], na[8], nwv[8];
     bool n_add = false;
-    if (NORM == 1 && !HS_FRESH(p)) {          // (early launch: these go out behind the wait, below)
+    if (NORM == 1) {
         const int D = p.K, ng = D >> 2;
         if (wave < p.M) {
             const int m = wave;
@@ -372,7 +305,7 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
         //  per CU run this prologue at once, the layer lost 6-32 us (profiles/r06_lat_probe_mid_rows_regression.txt).  One m-block chains use NORM == 3 instead.)
         const float4* sp = (const float4*)(p.ssq_in + (long)((mb0 + j) * 16 + (lane & 15)) * p.ssq_np);
 #pragma unroll
-        for (int t = 0; t < 8; ++t) { v[t] = make_float4(0.f, 0.f, 0.f, 0.f); if (hok[j] && q4n + 4 * t < np4) { const u32x4 r = car_ld16(sp + q4n + 4 * t, hs_fresh); v[t] = make_float4(__uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2]), __uint_as_float(r[3])); } }
+        for (int t = 0; t < 8; ++t) { v[t] = make_float4(0.f, 0.f, 0.f, 0.f); if (hok[j] && q4n + 4 * t < np4) { const u32x4 r = *(const u32x4*)(sp + q4n + 4 * t); v[t] = make_float4(__uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2]), __uint_as_float(r[3])); } }
     };
     auto ssq_finish = [&](const float4 (&v)[8], int j) {
         float sum = 0.f;
@@ -384,7 +317,6 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
     // Epilogue operands of this wave's FIRST epilogue unit (round 6): the residual values go out ahead of the weight stream, the RoPE row right behind it (its
     // address needs *pos: a scalar load requested here, waited for only after the stages are in flight) — in round 5 the epilogue started two dependent round
     // trips (pos -> rope row, or the residual load) after the fold.  Unconditional loads at clamped addresses; later units (u > wave) load in the loop as before.
-    // (Early launch: the residual stream was last written two kernels back — complete before this kernel was dispatched.)
     constexpr int IPc = I >= 2 ? I / 2 : 1, IWc = I >= 2 ? 2 : 1;
     const bool epi_first = wave < IPc * J && p.M <= 16;                  // wave-uniform; one m-block chains only (the latency-bound regime: elsewhere the extra prologue instructions cost more than the round trip)
     uint2 hv_h[IWc]; float4 cs_h[IWc];
@@ -414,56 +346,28 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
             }
         }
     };
-    if (hs_fresh) {
-        // ---- early launch: everything that does not depend on the predecessor first (weights of all stages, norm weight, RoPE row), then the wait, then X
-#pragma unroll
-        for (int d = 0; d < DEPTH; ++d) if (d < nkw) loadW(wr[d], nr[d], ku_lo + d);
-        rope_first();
-        HS_WAIT(p);
-        if (NORM == 1) {
-            const int D = p.K, ng = D >> 2;
-            if (wave < p.M) {
-                const int m = wave;
-                const bf16_t* src = p.nidx ? p.nemb + (long)p.nidx[m] * D : p.nh_in + (long)m * D;
-                const bf16_t* add = p.nadd ? p.nctrl + ((long)m * p.n_tok + (*p.pos - p.nT + 1)) * D : nullptr;
-                n_add = add != nullptr;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int gi = lane + q * 64;
-                    if (gi < ng) { nh[q] = car_ld8(src + gi * 4, p.nidx == nullptr); nwv[q] = *(const uint2*)(p.nw + gi * 4); if (add) na[q] = *(const uint2*)(add + gi * 4); }
-                }
-            }
+    if (NORM == 3 && s_nkbw > 0) {      // lane-dense DMA of this wave's X slice, norm-weight slice and the rows' partials (clamped chunk indices: every lane loads something valid)
+        const int c4 = s_nkbw * 4, xtot = p.M * c4, kb0 = ku_lo * XPU;
+        for (int r = 0; r < s_xr; ++r) {                            // wave-uniform trip count
+            int ci = lane + 64 * r; ci = ci < xtot ? ci : xtot - 1;
+            const int m = ci / c4, k8 = ci - m * c4;
+            __builtin_amdgcn_global_load_lds((car_gptr_t*)(p.nh_in + (long)m * p.K + kb0 * 32 + k8 * 8), (car_lptr_t*)(stg_x + (size_t)r * 1024), 16, 0, 0);
         }
-        if (NORM == 2) {
-#pragma unroll
-            for (int j = 0; j < J; ++j) { if (J <= 2) ssq_issue(sv[j], j); else { ssq_issue(sv[0], j); ssq_finish(sv[0], j); } }
+        { const int ci = lane < c4 ? lane : c4 - 1;
+          __builtin_amdgcn_global_load_lds((car_gptr_t*)(p.nw + kb0 * 32 + ci * 8), (car_lptr_t*)stg_w, 16, 0, 0); }
+        const int stot = p.M * (p.ssq_np >> 2), sr = (stot + 63) >> 6;
+        for (int r = 0; r < sr; ++r) {
+            int ci = lane + 64 * r; ci = ci < stot ? ci : stot - 1;
+            __builtin_amdgcn_global_load_lds((car_gptr_t*)(p.ssq_in + (long)ci * 4), (car_lptr_t*)(stg_s + (size_t)r * 1024), 16, 0, 0);
         }
-#pragma unroll
-        for (int d = 0; d < DEPTH; ++d) if (d < nkw) loadX(xr[d], ku_lo + d);
-    } else {
-        if (NORM == 3 && s_nkbw > 0) {      // lane-dense DMA of this wave's X slice, norm-weight slice and the rows' partials (clamped chunk indices: every lane loads something valid)
-            const int c4 = s_nkbw * 4, xtot = p.M * c4, kb0 = ku_lo * XPU;
-            for (int r = 0; r < s_xr; ++r) {                            // wave-uniform trip count
-                int ci = lane + 64 * r; ci = ci < xtot ? ci : xtot - 1;
-                const int m = ci / c4, k8 = ci - m * c4;
-                __builtin_amdgcn_global_load_lds((car_gptr_t*)(p.nh_in + (long)m * p.K + kb0 * 32 + k8 * 8), (car_lptr_t*)(stg_x + (size_t)r * 1024), 16, 0, 0);
-            }
-            { const int ci = lane < c4 ? lane : c4 - 1;
-              __builtin_amdgcn_global_load_lds((car_gptr_t*)(p.nw + kb0 * 32 + ci * 8), (car_lptr_t*)stg_w, 16, 0, 0); }
-            const int stot = p.M * (p.ssq_np >> 2), sr = (stot + 63) >> 6;
-            for (int r = 0; r < sr; ++r) {
-                int ci = lane + 64 * r; ci = ci < stot ? ci : stot - 1;
-                __builtin_amdgcn_global_load_lds((car_gptr_t*)(p.ssq_in + (long)ci * 4), (car_lptr_t*)(stg_s + (size_t)r * 1024), 16, 0, 0);
-            }
-        }
-        if (NORM == 2) {
-#pragma unroll
-            for (int j = 0; j < J; ++j) { if (J <= 2) ssq_issue(sv[j], j); else { ssq_issue(sv[0], j); ssq_finish(sv[0], j); } }
-        }
-#pragma unroll
-        for (int d = 0; d < DEPTH; ++d) if (d < nkw) load(wr[d], xr[d], nr[d], ku_lo + d);
-        rope_first();
     }
+    if (NORM == 2) {
+#pragma unroll
+        for (int j = 0; j < J; ++j) { if (J <= 2) ssq_issue(sv[j], j); else { ssq_issue(sv[0], j); ssq_finish(sv[0], j); } }
+    }
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) if (d < nkw) load(wr[d], xr[d], nr[d], ku_lo + d);
+    rope_first();
     STAMP(p, 6);                                                       // every load of the prologue has been issued
     if (NORM == 3) {
         // the DMA is invisible to the compiler's wait-count pass: the covering vmcnt is ours (MI355X_MICROARCH.md: nothing orders a ds_read behind a pending LDS-DMA
@@ -495,7 +399,7 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int gi = lane + q * 64;
-                    if (gi < ng) { nh[q] = car_ld8(src + gi * 4, hs_fresh && p.nidx == nullptr); if (add) na[q] = *(const uint2*)(add + gi * 4); }
+                    if (gi < ng) { nh[q] = *(const uint2*)(src + gi * 4); if (add) na[q] = *(const uint2*)(add + gi * 4); }
                 }
             }
             float val[8][4];
@@ -593,7 +497,7 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
             const int nkb2 = p.N >> 6;                                   // (N/2)/32
             const long off = ((((long)(m >> 4) * nkb2 + (hid >> 5)) * 64 + ((hid & 31) >> 3) * 16 + (m & 15)) << 3) + (hid & 7);
             uint2 o; o.x = pack_bf16x2(s[0], s[1]); o.y = pack_bf16x2(s[2], s[3]);
-            car_st8(p.outp + off, o, hs_wt);
+            *(uint2*)(p.outp + off) = o;
         } else {
             float ssq_acc = 0.f;
 #pragma unroll
@@ -611,7 +515,7 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
                     uint2 o;
                     o.x = pack_bf16x2(h0 + bf2f(f2bf(a[0])), h1 + bf2f(f2bf(a[1])));
                     o.y = pack_bf16x2(h2 + bf2f(f2bf(a[2])), h3 + bf2f(f2bf(a[3])));
-                    car_st8(hp, o, hs_wt);
+                    *(uint2*)hp = o;
                     if (p.ssq_out) {       // the squares of the STORED residual values: the next RMSNorm's row sum, one partial per (row, pair of row-blocks)
                         const float s0 = __uint_as_float(o.x << 16), s1 = __uint_as_float(o.x & 0xffff0000u), s2 = __uint_as_float(o.y << 16), s3 = __uint_as_float(o.y & 0xffff0000u);
                         ssq_acc += s0 * s0; ssq_acc += s1 * s1; ssq_acc += s2 * s2; ssq_acc += s3 * s3;
@@ -626,10 +530,10 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
                         if (p.kv8) {
                             unsigned char* vb = (unsigned char*)p.vc + sb + (long)(pos >> 5) * 2048 + (d0 >> 5) * 1024 + ((qv * 16 + (d0 & 15)) << 4) + ((d0 >> 4) & 1) * 8 + ev;
                             const int e01 = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(x0), sat448(x1), 0, false), e23 = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(x2), sat448(x3), 0, false);
-                            car_st1(vb, (unsigned char)(e01 & 0xff), hs_wt); car_st1(vb + 16, (unsigned char)((e01 >> 8) & 0xff), hs_wt); car_st1(vb + 32, (unsigned char)(e23 & 0xff), hs_wt); car_st1(vb + 48, (unsigned char)((e23 >> 8) & 0xff), hs_wt);
+                            vb[0] = (unsigned char)(e01 & 0xff); vb[16] = (unsigned char)((e01 >> 8) & 0xff); vb[32] = (unsigned char)(e23 & 0xff); vb[48] = (unsigned char)((e23 >> 8) & 0xff);
                         } else {
                             bf16_t* vb = p.vc + sb + ((long)(pos >> 5) * 4 + (d0 >> 4)) * 512 + ((qv * 16 + (d0 & 15)) << 3) + ev;
-                            car_st2(vb, f2bf(x0), hs_wt); car_st2(vb + 8, f2bf(x1), hs_wt); car_st2(vb + 16, f2bf(x2), hs_wt); car_st2(vb + 24, f2bf(x3), hs_wt);
+                            vb[0] = f2bf(x0); vb[8] = f2bf(x1); vb[16] = f2bf(x2); vb[24] = f2bf(x3);
                         }
                     } else {
                         const float4 cs = first_u ? cs_h[ii] : *(const float4*)(p.rope + ((long)pos * 32 + (d0 >> 1)) * 2);   // (cos, sin) of pairs d0/2, d0/2+1
@@ -640,27 +544,26 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_kernel(GemmDP p) {
                             uint2 o;
                             o.x = pack_bf16x2(bf2f(f2bf(r0)) * 0.125f, bf2f(f2bf(r1)) * 0.125f);
                             o.y = pack_bf16x2(bf2f(f2bf(r2)) * 0.125f, bf2f(f2bf(r3)) * 0.125f);
-                            car_st8(p.qout + ((long)m * p.H + hh) * 64 + d0, o, hs_wt);
+                            *(uint2*)(p.qout + ((long)m * p.H + hh) * 64 + d0) = o;
                         } else if (p.kv8) {       // rotated k: bf16 round (the Linear -> RoPE rounding points), then e4m3
                             unsigned char* kb_ = (unsigned char*)p.kc + sb + (long)(pos >> 4) * 1024 + ((((d0 & 31) >> 3) * 16 + (pos & 15)) << 4) + (d0 >> 5) * 8 + (d0 & 7);
                             int e = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(bf2f(f2bf(r0))), sat448(bf2f(f2bf(r1))), 0, false);
                             e = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(bf2f(f2bf(r2))), sat448(bf2f(f2bf(r3))), e, true);
-                            car_st4(kb_, (unsigned)e, hs_wt);
+                            *(unsigned*)kb_ = (unsigned)e;
                         } else {
                             uint2 o; o.x = pack_bf16x2(r0, r1); o.y = pack_bf16x2(r2, r3);
                             bf16_t* kb_ = p.kc + sb + ((long)(pos >> 4) * 2 + (d0 >> 5)) * 512 + ((((d0 & 31) >> 3) * 16 + (pos & 15)) << 3) + (d0 & 7);
-                            car_st8(kb_, o, hs_wt);
+                            *(uint2*)kb_ = o;
                         }
                     }
                 }
             }
             if (EPI == EPI_RESID && p.ssq_out) {       // lanes (c16, q4 = 0..3) hold the 4-column pieces of row m: fold them in a fixed order, one store per row
                 ssq_acc += __shfl_xor(ssq_acc, 16, 64); ssq_acc += __shfl_xor(ssq_acc, 32, 64);
-                if (q4 == 0) car_st4(p.ssq_out + (long)m * p.ssq_ld + (rb0 / IW + ip), __float_as_uint(ssq_acc), hs_wt);
+                if (q4 == 0) *(unsigned*)(p.ssq_out + (long)m * p.ssq_ld + (rb0 / IW + ip)) = __float_as_uint(ssq_acc);
             }
         }
     }
-    HS_ARRIVE(p);
 #ifdef CAR_STAMP
     __builtin_amdgcn_s_waitcnt(0); STAMP(p, 5);
 #endif
@@ -960,10 +863,8 @@ __global__ __launch_bounds__(1024) void dec_attn2s_kernel(Attn2P p) {
     const u32x4* Kp = KV8 ? (const u32x4*)((const unsigned char*)p.kc + sbase) + lane : (const u32x4*)(p.kc + sbase) + lane;
     const u32x4* Vp = KV8 ? (const u32x4*)((const unsigned char*)p.vc + sbase) + lane : (const u32x4*)(p.vc + sbase) + lane;
     const bf16_t* qp = p.q + ((long)b * p.H + h) * 64;
-    bf16x8 qf0, qf1;                                                    // loaded behind the K / V requests (and behind the early-launch wait: the predecessor writes q)
+    bf16x8 qf0, qf1;                                                    // loaded behind the K / V requests
     const int nblk = (pos >> 5) + 1;
-    const bool hs_fresh = HS_FRESH(p), hs_wt = HS_WT(p);
-    const int lastb = nblk - 1;                                         // the block that holds the new token's K / V row: written by the predecessor (wqkv)
     float m_run = -INFINITY, l_run = 0.f;
     f32x4 o[4];
 #pragma unroll
@@ -971,17 +872,10 @@ __global__ __launch_bounds__(1024) void dec_attn2s_kernel(Attn2P p) {
     const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     constexpr int NL = KV8 ? 2 : 4;
     auto loadkv = [&](u32x4 (&kr)[4], u32x4 (&vr)[4], int blk) {
-        if (hs_fresh && blk == lastb) {                                 // wave-uniform
 #pragma unroll
-            for (int i = 0; i < NL; ++i) kr[i] = car_ld16(Kp + ((long)blk * NL + i) * 64, true);
+        for (int i = 0; i < NL; ++i) kr[i] = __builtin_nontemporal_load(Kp + ((long)blk * NL + i) * 64);
 #pragma unroll
-            for (int i = 0; i < NL; ++i) vr[i] = car_ld16(Vp + ((long)blk * NL + i) * 64, true);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NL; ++i) kr[i] = __builtin_nontemporal_load(Kp + ((long)blk * NL + i) * 64);
-#pragma unroll
-            for (int i = 0; i < NL; ++i) vr[i] = __builtin_nontemporal_load(Vp + ((long)blk * NL + i) * 64);
-        }
+        for (int i = 0; i < NL; ++i) vr[i] = __builtin_nontemporal_load(Vp + ((long)blk * NL + i) * 64);
     };
     unsigned ma[8];
     auto compute = [&](const u32x4 (&kr_)[4], const u32x4 (&vr_)[4], int blk, bool use_mk) {
@@ -1038,14 +932,9 @@ __global__ __launch_bounds__(1024) void dec_attn2s_kernel(Attn2P p) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) ma[e] = mk[min(jb + (e < 4 ? e : 12 + e), p.T - 1)];
         }
-        // early launch: the history blocks are requested BEFORE the wait (they were written by earlier steps), the block of the new row and q behind it
-        const bool a_pre = cur < nblk && !(hs_fresh && cur == lastb), b_pre = cur + 16 < nblk && !(hs_fresh && cur + 16 == lastb);
-        if (a_pre) loadkv(ka, va, cur);
-        if (b_pre) loadkv(kb2, vb2, cur + 16);
-        HS_WAIT(p);
-        { const u32x4 q0 = car_ld16(qp + q4 * 8, hs_fresh), q1 = car_ld16(qp + 32 + q4 * 8, hs_fresh); qf0 = *(const bf16x8*)&q0; qf1 = *(const bf16x8*)&q1; }
-        if (cur < nblk && !a_pre) loadkv(ka, va, cur);
-        if (cur + 16 < nblk && !b_pre) loadkv(kb2, vb2, cur + 16);
+        if (cur < nblk) loadkv(ka, va, cur);
+        if (cur + 16 < nblk) loadkv(kb2, vb2, cur + 16);
+        { const u32x4 q0 = *(const u32x4*)(qp + q4 * 8), q1 = *(const u32x4*)(qp + 32 + q4 * 8); qf0 = *(const bf16x8*)&q0; qf1 = *(const bf16x8*)&q1; }
         bool first = true;
         while (cur < nblk) {
             compute(ka, va, cur, first && mk_a);
@@ -1082,9 +971,8 @@ __global__ __launch_bounds__(1024) void dec_attn2s_kernel(Attn2P p) {
         long off;
         if (p.out_packed) off = ((((long)(b >> 4) * (p.dim >> 5) + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (b & 15)) << 3) + (k & 7);
         else off = (long)b * p.dim + k;
-        car_st2(p.out + off, f2bf(O / L), hs_wt);
+        p.out[off] = f2bf(O / L);
     }
-    HS_ARRIVE(p);
 #ifdef CAR_STAMP
     __builtin_amdgcn_s_waitcnt(0); STAMP(p, 5);
 #endif
@@ -1238,8 +1126,6 @@ __global__ __launch_bounds__(256) void rmsnorm2_kernel(Norm2P p, int rows) {
     }
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     STAMP(p, 0);
-    const bool hs_fresh = HS_FRESH(p), hs_wt = HS_WT(p);
-    HS_WAIT(p);                                                            // early launch: the residual stream comes from the predecessor
     if (r < rows) {
     const int lane = threadIdx.x & 63;
     const int D = p.D, ng = D >> 2;
@@ -1255,7 +1141,7 @@ __global__ __launch_bounds__(256) void rmsnorm2_kernel(Norm2P p, int rows) {
     for (int q = 0; q < NQ; ++q) {
         const int gi = lane + q * 64;
         if (gi < ng) {
-            const uint2 u = car_ld8(src + gi * 4, hs_fresh && p.idx == nullptr);
+            const uint2 u = *(const uint2*)(src + gi * 4);
             float v[4] = {__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
             if (add) {
                 const uint2 a = *(const uint2*)(add + gi * 4);
@@ -1277,7 +1163,7 @@ __global__ __launch_bounds__(256) void rmsnorm2_kernel(Norm2P p, int rows) {
         const int gi = lane + q * 64;
         if (gi < ng) {
             const int k = gi * 4;
-            if (p.h_out) { uint2 u; u.x = pack_bf16x2(val[q][0], val[q][1]); u.y = pack_bf16x2(val[q][2], val[q][3]); car_st8(p.h_out + r * D + k, u, hs_wt); }
+            if (p.h_out) { uint2 u; u.x = pack_bf16x2(val[q][0], val[q][1]); u.y = pack_bf16x2(val[q][2], val[q][3]); *(uint2*)(p.h_out + r * D + k) = u; }
             const uint2 wu = wreg[q];
             const float w[4] = {__uint_as_float(wu.x << 16), __uint_as_float(wu.x & 0xffff0000u), __uint_as_float(wu.y << 16), __uint_as_float(wu.y & 0xffff0000u)};
             float o[4];
@@ -1285,11 +1171,10 @@ __global__ __launch_bounds__(256) void rmsnorm2_kernel(Norm2P p, int rows) {
             for (int e = 0; e < 4; ++e) o[e] = bf2f(f2bf(val[q][e] * rstd)) * w[e];
             uint2 u; u.x = pack_bf16x2(o[0], o[1]); u.y = pack_bf16x2(o[2], o[3]);
             const long off = ((((r >> 4) * nkb + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (r & 15)) << 3) + (k & 7);
-            car_st8(p.xn + off, u, hs_wt);
+            *(uint2*)(p.xn + off) = u;
         }
     }
     }
-    HS_ARRIVE(p);
 #ifdef CAR_STAMP
     __builtin_amdgcn_s_waitcnt(0); STAMP(p, 5);
 #endif

@@ -31,7 +31,6 @@ struct Dims { int M, D, Fh, H, SA, T, pos; };
 struct Bufs { bf16_t *W, *kv, *h, *xn, *att, *mid, *q, *nw; float *part, *rope, *ssq; int *dpos; long long* stamp; size_t per_layer, kvper; };
 static bool g_normx = true;
 static int g_pf_mode = 0, g_pf_attn = 192, g_pf_lin = 160, g_attn_small = 1, g_overlap = 0, g_pf_kv = 0;
-static unsigned* g_cnt = nullptr; static unsigned* g_err = nullptr; static int g_prev_wgs = 0; static hipStream_t g_side = nullptr;      // early launch: per-kernel arrival counters (8 shards x 32 uints)
 struct KInfo { std::string name; int wgs; int main; };      // main: workgroups that do the kernel's work (the rest are L2 run-ahead helpers)
 static std::vector<KInfo> g_k;          // kernels in launch order (slot = index)
 
@@ -51,17 +50,7 @@ static void layer(const Dims& d, const Bufs& b, int l, int NL, hipStream_t st, i
         p.stamp = b.stamp; p.stamp_slot = slot(nb, (N / (16 * I)) * ((Mb + J - 1) / J), p.pf_wgs);
         if (p.ssq_out) p.ssq_ld = N / (16 * (I >= 2 ? 2 : 1));
         if (p.ssq_in) p.ssq_np = D / (16 * (car_pick_gemm_cfg(M, D, D, EPI_RESID) / 100 >= 2 ? 2 : 1));      // (the probe only times: wo's partial count serves both consumers; the buffer holds the maximum)
-        hipStream_t ks = st;
-#ifdef CAR_EARLY_LAUNCH
-        if (g_overlap) {
-            const int kidx = p.stamp_slot;
-            ks = (kidx & 1) ? g_side : st;
-            if (kidx > 0) { p.dep = g_cnt + (size_t)(kidx - 1) * 256; p.dep_n = g_prev_wgs; }
-            p.done = g_cnt + (size_t)kidx * 256; p.hs_err = g_err;
-            g_prev_wgs = (N / (16 * I)) * ((Mb + J - 1) / J);
-        }
-#endif
-        if (car_launch_dec_gemm_cfg(&p, epi, cfg, ks)) { printf("cfg %d rejected (N=%d K=%d)\n", cfg, N, K); exit(3); }
+        if (car_launch_dec_gemm_cfg(&p, epi, cfg, st)) { printf("cfg %d rejected (N=%d K=%d)\n", cfg, N, K); exit(3); }
     };
     GemmDP z; memset(&z, 0, sizeof(z));
     auto norm = [&](const bf16_t* hin) { Norm2P n; memset(&n, 0, sizeof(n)); n.h_in = hin; n.xn = b.xn; n.w = b.nw; n.D = D; n.eps = 1e-5f; n.stamp = b.stamp; n.stamp_slot = slot("rmsnorm2", (M + 3) / 4); car_launch_rmsnorm2(&n, M, st); };
@@ -85,18 +74,7 @@ static void layer(const Dims& d, const Bufs& b, int l, int NL, hipStream_t st, i
             a.pf_p0 = wo; a.pf_b0 = (unsigned)((size_t)D * D * 2); a.pf_p1 = w13; a.pf_b1 = (unsigned)((size_t)2 * Fh * D * 2);
         }
         a.stamp = b.stamp; a.stamp_slot = slot(nb, d.H * M * ns, a.pf_wgs);
-        hipStream_t ks = st;
-#ifdef CAR_EARLY_LAUNCH
-        if (g_overlap) {
-            if (av != 162) { printf("early launch needs the small-batch attention (variant 162)\n"); exit(3); }
-            const int kidx = a.stamp_slot;
-            ks = (kidx & 1) ? g_side : st;
-            if (kidx > 0) { a.dep = g_cnt + (size_t)(kidx - 1) * 256; a.dep_n = g_prev_wgs; }
-            a.done = g_cnt + (size_t)kidx * 256; a.hs_err = g_err;
-            g_prev_wgs = d.H * M;
-        }
-#endif
-        car_launch_dec_attn2_var(&a, M, av, 0, ks);
+        car_launch_dec_attn2_var(&a, M, av, 0, st);
     }
     { GemmDP q = z; q.h = b.h; if (nx) q.ssq_out = b.ssq;
       if (g_pf_mode == 2) { q.pf_wgs = g_pf_lin; q.pf_p0 = w2; q.pf_b0 = (unsigned)((size_t)D * Fh * 2); }
@@ -121,12 +99,10 @@ int main(int argc, char** argv) {
     if (argc > 6) g_pf_mode = atoi(argv[6]);           // L2 run-ahead helper workgroups (decode2_params.h CAR_PF_FIELDS): see the mode line printed below
     if (argc > 7) g_pf_attn = atoi(argv[7]);
     if (argc > 8) g_pf_lin = atoi(argv[8]);
-    if (argc > 9) g_attn_small = atoi(argv[9]);
-    if (argc > 10) g_overlap = atoi(argv[10]);
+    if (argc > 9) g_attn_small = atoi(argv[9]);        // 0: the round-3 one-launch attention (variant 160) instead of round 6's dec_attn2s_kernel (162)
+    if (argc > 10) g_overlap = atoi(argv[10]);         // reserved (was: early launch): must be 0
     if (argc > 11) g_pf_kv = atoi(argv[11]);            // 1: w2's helpers also touch the KV prefixes of the next layer's attention
-#ifndef CAR_EARLY_LAUNCH
-    if (g_overlap) { printf("early launch: build with -DCAR_EARLY_LAUNCH\n"); return 2; }
-#endif          // 1: early launch — the chain alternates between two streams, dependencies through arrival counters (decode2_params.h CAR_HS_FIELDS)        // 0: the round-3 one-launch attention (variant 160) instead of round 6's dec_attn2s_kernel (162)
+    if (g_overlap) { printf("early launch (argument 10) was removed from the decode kernels; the last commit that has it is c0e7aea\n"); return 2; }
     const int M16 = (d.M + 15) / 16 * 16;
     Bufs b; memset(&b, 0, sizeof(b));
     b.per_layer = (size_t)(3 * d.D * d.D + d.D * d.D + 2 * d.Fh * d.D + d.D * d.Fh);
@@ -153,35 +129,18 @@ int main(int argc, char** argv) {
     printf("rows %d, position %d, %d distinct layers per graph: %.1f MB of weights + %.1f MB of KV rows per layer; HBM floor %.1f us per layer at 6.3 TB/s\n",
            d.M, d.pos, NL, wbytes / 1e6, kvbytes / 1e6, (wbytes + kvbytes) / 6.3e6);
     hipGraph_t graph = nullptr; hipGraphExec_t ex = nullptr;
-    hipEvent_t ef, ej; CK(hipEventCreateWithFlags(&ef, hipEventDisableTiming)); CK(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
-    if (g_overlap) {
-        CK(hipStreamCreateWithFlags(&g_side, hipStreamNonBlocking));
-        g_cnt = dalloc<unsigned>((size_t)NL * 8 * 256 + 64); g_err = g_cnt + (size_t)NL * 8 * 256;
-        CK(hipMemset(g_cnt, 0, ((size_t)NL * 8 * 256 + 64) * 4));
-    }
-    // early launch: TWO single-branch graphs, one per stream (a two-branch graph is submitted by the host node by node, branch after branch — ~9.5 us per node,
-    // measured: the branches never ran side by side), launched back to back every replay; the counters are cleared and the streams joined around them by events
-    hipGraph_t graphB = nullptr; hipGraphExec_t exB = nullptr;
     CK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    if (g_overlap) CK(hipStreamBeginCapture(g_side, hipStreamCaptureModeThreadLocal));
     for (int l = 0; l < NL; ++l) layer(d, b, l, NL, st, opt);
     CK(hipStreamEndCapture(st, &graph));
-    if (g_overlap) { CK(hipStreamEndCapture(g_side, &graphB)); CK(hipGraphInstantiate(&exB, graphB, nullptr, nullptr, 0)); printf("EARLY LAUNCH: kernels alternate between two streams (one single-branch graph each), dependencies through arrival counters\n"); }
     if (g_pf_mode) printf("L2 run-ahead helpers: mode %d (1: attention hosts wo + w1|w3, w2 hosts the next wqkv; 2: + wo hosts w2; 3: attention hosts wo + w1|w3 + nothing else), %d helper workgroups beside the attention, %d beside wo / w2\n", g_pf_mode, g_pf_attn, g_pf_lin);
     CK(hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0));
-    auto replay = [&]() {
-        if (!g_overlap) { CK(hipGraphLaunch(ex, st)); return; }
-        CK(hipMemsetAsync(g_cnt, 0, (size_t)NL * 8 * 256 * 4, st)); CK(hipEventRecord(ef, st)); CK(hipStreamWaitEvent(g_side, ef, 0));
-        CK(hipGraphLaunch(ex, st)); CK(hipGraphLaunch(exB, g_side));
-        CK(hipEventRecord(ej, g_side)); CK(hipStreamWaitEvent(st, ej, 0));
-    };
+    auto replay = [&]() { CK(hipGraphLaunch(ex, st)); };
     for (int i = 0; i < 3; ++i) replay();
     CK(hipStreamSynchronize(st));
     CK(hipEventRecord(t0, st));
     for (int i = 0; i < REPS; ++i) replay();
     CK(hipEventRecord(t1, st)); CK(hipEventSynchronize(t1));
     float ms = 0; CK(hipEventElapsedTime(&ms, t0, t1)); CK(hipGetLastError());
-    if (g_overlap) { unsigned e = 0; CK(hipMemcpy(&e, g_err, 4, hipMemcpyDeviceToHost)); printf("early-launch error word: %u (0 = no wait gave up)\n", e); }
     const int KPL = (int)g_k.size() / NL;
     printf("instrumented chain: %.2f us per layer (%d kernels per layer + combine where split)\n", ms * 1000.0 / (REPS * NL), KPL);
     std::vector<long long> hs(nstamp);

@@ -4,7 +4,6 @@
 # gpurun_out/<target>/.  Copy what is to be judged into profiles/.
 #   small-chain   lat_probe: phase timeline of a decode layer at 2 / 8 / 16 rows, with and without the L2 run-ahead helpers, three positions
 #   mid-chain     lat_probe at 24 / 32 / 48 / 64 / 128 rows (the NORM == 2 regime and above)
-#   early-launch  lat_probe built with -DCAR_EARLY_LAUNCH: two streams + arrival counters (measured, not shipped)
 #   caches        xk_cache (what a kernel boundary keeps: L2 / Infinity Cache) and xk_fresh (first-load latency by what a kernel reads)
 #   kbench        correctness of every decode2.hip kernel / tile configuration against host references (+ timing with `kbench-perf`)
 #   twins         tools/twin_probe.py: two chains, free-running twin rows (GPT-B, 384 sequences)
@@ -21,9 +20,6 @@ case $T in
   mid-chain)
     need lat_probe -DCAR_STAMP experiments/lat_probe.hip
     for r in 24 32 48 64 128; do lat rows$r $r 631; done ;;
-  early-launch)
-    need lat_probe_el -DCAR_STAMP -DCAR_EARLY_LAUNCH experiments/lat_probe.hip
-    for r in 2 8; do timeout 60 experiments/lat_probe_el $r 631 0 1 12 0 0 0 1 1 > $O/rows$r.txt 2>&1; grep -H "instrumented chain\|error word" $O/rows$r.txt; done ;;
   caches)
     need xk_cache experiments/xk_cache.hip; need xk_fresh experiments/xk_fresh.hip
     timeout 300 experiments/xk_cache | tee $O/xk_cache.txt; timeout 120 experiments/xk_fresh | tee $O/xk_fresh.txt ;;
