@@ -594,7 +594,8 @@ static void launch_gemm_ij(const GemmDP& p_, int epi, hipStream_t st) {
 }
 
 // tile shape: I row-blocks x J m-blocks per workgroup, WAVES waves splitting K.  cfg = I*100 + J*10 + (WAVES == 8)
-extern "C" int car_launch_dec_gemm_cfg(const GemmDP* p, int epi, int cfg, hipStream_t st) {
+// `staged_ok`: the staged on-the-fly norm (NORM == 3) may be chosen where it applies (car_launch_dec_gemm_cfg: always)
+extern "C" int car_launch_dec_gemm_cfg_ex(const GemmDP* p, int epi, int cfg, int staged_ok, hipStream_t st) {
     if (epi == EPI_SWIGLU && cfg < 200) return -1;       // the (a, c) pair needs two adjacent row-blocks in one tile
     if (p->N % (16 * (cfg / 100)) || p->K % 32) return -1;
     if (p->wscale && p->K % 64) return -1;
@@ -605,7 +606,7 @@ extern "C" int car_launch_dec_gemm_cfg(const GemmDP* p, int epi, int cfg, hipStr
         // (one DMA instruction for the norm weight) and at least one k-unit for every wave.
         {
             const int nku = p->K / (f8 ? 64 : 32), nkw_max = (nku + 7) / 8;
-            if (p->M <= 16 && (cfg / 10) % 10 == 1 && cfg % 10 == 1 && nku >= 8 && nkw_max * (f8 ? 2 : 1) <= 16 && !CAR_KNOB("CAR_NO_STAGED_NORMX")) {
+            if (p->M <= 16 && (cfg / 10) % 10 == 1 && cfg % 10 == 1 && nku >= 8 && nkw_max * (f8 ? 2 : 1) <= 16 && staged_ok) {
                 switch (cfg / 100) {
 #define CASE3(I) case I: if (f8 == 2) launch_gemm_ij<I, 1, 8, 2, 3>(*p, epi, st); else if (f8) launch_gemm_ij<I, 1, 8, 1, 3>(*p, epi, st); else launch_gemm_ij<I, 1, 8, 0, 3>(*p, epi, st); return 0;
                     CASE3(1) CASE3(2) CASE3(4)
@@ -647,6 +648,7 @@ extern "C" int car_launch_dec_gemm_cfg(const GemmDP* p, int epi, int cfg, hipStr
     return 0;
 }
 
+extern "C" int car_launch_dec_gemm_cfg(const GemmDP* p, int epi, int cfg, hipStream_t st) { return car_launch_dec_gemm_cfg_ex(p, epi, cfg, 1, st); }
 // tile choice from the MI355X sweep of experiments/kbench.hip (profiles/r02_kbench.txt): XL shapes at M = 256/128/64/16/2
 extern "C" int car_pick_gemm_cfg(int M, int N, int K, int epi) {
     const int Mb = (M + 15) / 16;

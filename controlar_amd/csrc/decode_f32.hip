@@ -492,13 +492,11 @@ extern "C" int car_pick_gemm_f32_cfg2(int M, int N, int K, int epi, int chains) 
     const int reg = I * 10 + (Mb >= 2 ? 2 : 1);
     if (K % 128 || N % 64) return reg;
     if (epi == FEPI_RESID) {
-        { const char* ev = CAR_KNOB("CAR_F32_RESID_CFG"); if (ev && M >= 64) return atoi(ev); }
         if (M >= 320) return 1214;
         return chains >= 3 && M >= 96 ? 1212 : reg;
     }
     if (N >= 16384) return M >= 64 ? 1212 : reg;
     if (N >= 4096) return M >= 128 || (chains >= 2 && M >= 96) ? 1212 : reg;
-    { const char* ev = CAR_KNOB("CAR_F32_QKV_TILED_FROM"); if (ev) return M >= atoi(ev) ? 1212 : reg; }
     return M >= 320 || (chains >= 2 && M >= 96) ? 1212 : reg;
 }
 extern "C" int car_pick_gemm_f32_cfg(int M, int N, int K, int epi) { return car_pick_gemm_f32_cfg2(M, N, K, epi, 1); }

@@ -3,62 +3,170 @@
 #include "engine_internal.h"
 
 // ------------------------------------------------------------------------------------- decode step (one token for all b sequences)
-struct StepBufs { void *h, *xn, *qkv, *att, *mid, *mid2; float* part; float* logits; int *pos, *step, *cur; };
-
 // A chain = a contiguous slice [b0, b0+bg) of the sequences decoded as its own dependency chain.  With several chains the
 // captured step has parallel branches: one chain's HBM-bound attention overlaps the other chains' latency-bound GEMMs
 // (each chain re-streams the weights; a layer's 40 MB sits in the 256 MiB MALL between chains).
+// DecodePlan: everything the captured step depends on beyond shapes and pointers — the schedule.  plan_decode() fills it once per generate call (before the
+// buffers are sized: the arena in c->dec_parts depends on each chain's nsplit) and is the ONLY reader of the development switches for the decode loop; the
+// step builders read the plan and StepBufs, and the plan's bytes are the first half of the graph-cache key (generate_impl).
+enum { RA_NONE = 0, RA_SMALL, RA_NX, RA_MID, kEarlyChain = 8, kNoOverride = -0x7fffffff };      // RA_*: L2 run-ahead form of a chain (plan_decode)
+struct ChainPlan {
+    int b0, bg, nsplit;
+    int attn_variant, attn_lds_pad, attn_pgrid;      // attn_variant: the decode2.hip variant (fast) / the `fused` form of car_launch_dec_attn_f32_ex (exact)
+    int fuse_norm, normx, normx_max, normx_j4, staged_normx;      // the norms: GEMM prologue (<= 8 rows) / on the fly (<= normx_max rows; staged = NORM == 3 allowed) / rmsnorm2 launches
+    int runahead, kv_runahead;                       // RA_*; the KV prefixes ride on w2's helpers (MEASURED, OFF)
+};
+struct DecodePlan {
+    int mode, NG, mult, img0[9];                     // chain g = images [img0[g], img0[g+1]), `mult` rows per image ([cond | uncond] under CFG)
+    int phase, gsteps, lin_prio, no_graph;           // phase offset between the chains, tokens per captured graph, raised wave priority of the linears / norms, eager launches
+    int n_early;                                     // exact mode, three chains: the first n_early steps run as ONE chain, ch[kEarlyChain]
+    int f32_resid_cfg, f32_qkv_tiled_from;           // exact-mode tile overrides on top of car_pick_gemm_f32_cfg2's answer (kNoOverride: none)
+    ChainPlan ch[9];
+};
+static int attn_splits(int wg) { int n = 1; while (wg * n < 1024 && n < 16) n *= 2; return n; }      // fast mode: split-KV factor that gives `wg` (sequence, head) pairs 1024 workgroups
+
+// `nsteps`, `skip`: decode steps of this call and the positions CAR_DEBUG_SKIP_STEPS starts late.  Touches no device state.
+static void plan_decode(DecodePlan& pl, const car_config& g, int mode, int n_cu, int B, bool use_cfg, int S_max, int nsteps, int skip, bool has_mask) {
+    memset(&pl, 0, sizeof(pl));
+    const bool fast = mode == CAR_BF16;
+    const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, T = g.cls_token_num;
+    const int mult = use_cfg ? 2 : 1, b = mult * B;
+    auto num = [](const char* v, int dflt) { return v ? atoi(v) : dflt; };
+    // ---- the switches of the development library (all null in the shipped one), each read once
+    const char *k_chains = CAR_KNOB("CAR_CHAINS"), *k_one_max = CAR_KNOB("CAR_ONE_LAUNCH_MAX"), *k_variant = CAR_KNOB("CAR_ATTN_VARIANT"), *k_phase = CAR_KNOB("CAR_PHASE_OFFSET"), *k_form = CAR_KNOB("CAR_ATTN_F32_FORM");
+    const bool single_chain = CAR_KNOB("CAR_SINGLE_CHAIN"), no_early = CAR_KNOB("CAR_NO_EARLY_CHAIN"), split_small = CAR_KNOB("CAR_ATTN_SPLIT_SMALL"), old_small = CAR_KNOB("CAR_ATTN_OLD_SMALL");
+    const bool no_runahead = CAR_KNOB("CAR_NO_RUNAHEAD"), no_small_fuse = CAR_KNOB("CAR_NO_SMALL_FUSE"), no_normx = CAR_KNOB("CAR_NO_NORMX"), kv_runahead = CAR_KNOB("CAR_KV_RUNAHEAD"), no_staged = CAR_KNOB("CAR_NO_STAGED_NORMX");
+    const int k_nsplit = num(CAR_KNOB("CAR_ATTN_NSPLIT"), 0), k_persist = num(CAR_KNOB("CAR_ATTN_PERSIST"), 0), lds_pad = num(CAR_KNOB("CAR_ATTN_LDS_PAD"), 0);      // A/B: shorter attention workgroups / persistent grid
+    const int normx_max = num(CAR_KNOB("CAR_NORMX_MAX"), 48), normx_j4 = num(CAR_KNOB("CAR_NORMX_J4"), 0) != 0, k_gsteps = num(CAR_KNOB("CAR_GRAPH_STEPS"), 1);
+    pl.mode = mode; pl.mult = mult; pl.lin_prio = num(CAR_KNOB("CAR_LINEAR_PRIO"), 0) != 0;
+    pl.no_graph = CAR_KNOB("CAR_NO_GRAPH") != nullptr;      // profiling aid: eager launches (PMC collection cannot follow graph replays)
+    pl.f32_resid_cfg = num(CAR_KNOB("CAR_F32_RESID_CFG"), kNoOverride); pl.f32_qkv_tiled_from = num(CAR_KNOB("CAR_F32_QKV_TILED_FROM"), kNoOverride);
+
+    // ---- chains.  Two from 192 sequences up: each chain's GEMMs stream the weights once for <= 128+ rows, and one chain's HBM-bound
+    // attention runs beside the other's latency-bound GEMMs (profiles/r02_decode_chain_sweep.txt)
+    // (exact mode, round 4: the same cut — its linears are bound by the fp32 matrix pipe and its attention by HBM, so the two chains overlap DIFFERENT resources;
+    //  the rows of a chain are computed exactly as in any other batch, so the cut does not touch the mode's batch invariance)
+    int NG = b >= 192 ? 2 : 1;
+    // exact mode, round 5 (profiles/r05_exact_probe_*.txt, 384 sequences, mean position, ms per step): 1 chain 18.50, 2 chains 18.10, 3 chains 17.42, 4 chains
+    // 19.24, 6 chains 21.96.  The attention runs as 12-wave workgroups (decode_f32.hip: 24 of a CU's 32 wave slots), so the other chains' linears are resident
+    // beside it; a chain's four linears have to finish while the OTHER chains stream their KV, and with three chains that window is two attentions long.
+    if (!fast && b >= 288) NG = 3;
+    if (k_chains) { const int v = atoi(k_chains); if (v >= 1 && v <= 8 && B / v >= 2) NG = v; }
+    if (single_chain || NG > B) NG = 1;
+    pl.NG = NG; for (int gi = 0; gi <= NG; ++gi) pl.img0[gi] = (int)((long)B * gi / NG);
+    // ---- decode-loop schedule knobs, all OFF by default in fast mode: the MI355X sweeps of tools/overlap_sweep.py found none of them worth a
+    // per cent (profiles/r02_overlap_sweep_v1..v3, DESIGN.md §4 — a linear beside the bandwidth-saturating attention makes no progress whatever
+    // the schedule); they stay as A/B switches, and tests/test_parity_gpu.py pins that none of them changes a token.
+    //   phase offset : with >= 2 chains, chain g+1 enters the step right after chain g's first wqkv (see enqueue_decode_step_fast)
+    //   graph steps  : consecutive tokens captured per graph replay — the chains free-run across them (one fork / join and one phase
+    //                  offset per `gsteps` tokens instead of per token); the remainder runs on a single-step graph
+    //   linear prio  : s_setprio on the linears / norms
+    pl.phase = NG >= 2 && (k_phase ? atoi(k_phase) != 0 : !fast);      // exact mode: the second chain enters half a layer late, so that attention meets linears, not attention
+    pl.gsteps = fast && k_gsteps >= 1 && k_gsteps <= 64 ? k_gsteps : 1;
+    const int nsplit_exact = (S_max + AF_SPLIT - 1) / AF_SPLIT;
+    const bool fused = (long)Hn * b >= 2048 && nsplit_exact <= 8;
+    // several chains: 12-wave attention workgroups (two per CU = 24 of its 32 wave slots), so that the other chain's linears find room beside it
+    auto plan_exact = [&](ChainPlan& cp) { cp.nsplit = nsplit_exact; cp.attn_variant = fused ? num(k_form, cp.bg < b ? 3 : 1) : 0; };
+    for (int gi = 0; gi < NG; ++gi) {
+        ChainPlan& cp = pl.ch[gi]; const int bg = mult * (pl.img0[gi + 1] - pl.img0[gi]);
+        cp.b0 = mult * pl.img0[gi]; cp.bg = bg;
+        if (!fast) { plan_exact(cp); continue; }      // exact mode: a chain is a row range of the shared row-major buffers
+        // a handful of sequences (<= 240 (sequence, head) pairs = 12 XL sequences): ONE launch of 16-wave workgroups instead of split-KV + combine —
+        // one dependent kernel less per layer.  tools/small_ab.py on MI355X (XL, 1024 tokens, ms per step, same process): 2 rows 1.548 -> 1.406,
+        // 8 rows 1.611 -> 1.465, 12 rows 1.887 -> 1.725; at 16 rows the split form wins again (1.890 vs 1.923)  [profiles/r03_small_ab.txt]
+        // (round 6: with dec_attn2s — two blocks in flight per wave — the one-launch form wins up to 24 XL sequences: 38.8 -> 38.1 us per layer at 16 rows, 47.5 -> 45.9 at 20,
+        //  48.4 -> 46.9 at 24, tools/mid_ab.py with CAR_ONE_LAUNCH_MAX; 480 sixteen-wave workgroups still fit the chip in one round)
+        const bool one_launch = (long)bg * Hn <= num(k_one_max, T <= 512 ? 480 : 240) && !split_small;
+        cp.nsplit = one_launch ? 1 : attn_splits(bg * Hn);
+        if (k_nsplit == 1 || k_nsplit == 2 || k_nsplit == 4 || k_nsplit == 8 || k_nsplit == 16) cp.nsplit = k_nsplit;
+        // attention variant (decode2.hip; profiles/r02_kbench_*): 4 waves per (sequence, head) from 128 sequences up, 2 below; 16 in the one-launch small form
+        // (round 6: the one-launch form is dec_attn2s_kernel, variant 162 — two blocks in flight per wave, bit-identical to 160; it needs T <= 512 and the jmin table)
+        cp.attn_variant = (one_launch && cp.nsplit == 1) ? ((T <= 512 && !old_small) ? 162 : 160) : ((cp.nsplit == 1 && bg < 128) ? 20 : 40);
+        cp.attn_variant = num(k_variant, cp.attn_variant); cp.attn_lds_pad = lds_pad;
+        // persistent attention grid: R resident workgroups per CU walk the (sequence, head) items in equal shares
+        if (k_persist > 0 && k_persist <= 16 && cp.nsplit == 1) { const long items = (long)bg * Hn, cap = (long)n_cu * k_persist;
+            if (items > cap) { const long per = (items + cap - 1) / cap; cp.attn_pgrid = (int)((items + per - 1) / per); }
+        }
+        // tiny chains (<= 8 rows): the latency-bound regime (BASELINE configs 2, 4, 5).  The two RMSNorms of a layer and the final norm run
+        // in the prologue of the GEMM that consumes them (dec_gemm NORM variant), and the attention is ONE launch of 16-wave workgroups
+        // (no split-KV partials, no combine kernel): 5 dependent kernels per layer instead of 8.  Measured on MI355X with the layer loop of
+        // experiments/small_chain (profiles/r03_small_chain.txt, position 631, us per layer): 2 rows 40.2 -> 35.2, 4 rows 41.6 -> 35.7,
+        // 8 rows 47.8 -> 37.4 with 8-wave tiles (one row of the prologue norm per wave); from 12 rows up the fused prologue (every workgroup
+        // repeats the norm of all rows) no longer wins (44.1 either way at 12, 50.1 vs 49.4 at 16) and the separate norm kernels stay.
+        // The floor of this structure is the kernel boundary itself: 5 EMPTY kernels per layer cost 8.3 us.
+        cp.fuse_norm = bg <= 8 && D <= 2048 && !no_small_fuse;
+        // chains of up to 48 rows (round 4, experiments/lat_probe: profiles/r04_lat_probe_v5_*): the RMSNorm in front of wqkv / w1|w3 / output is applied ON THE FLY.
+        // The RESID linear that produced the residual stream (wo, w2) leaves each row's sum of squares as per-tile partials; the consumer folds them into rstd
+        // and normalises the bf16 residual rows it loads as its X operand in registers (dec_gemm NORM == 2).  Against the prologue form (<= 8 rows: a barrier-
+        // separated norm in front of the main loop, 3.6-6.0 us of a 6-8 us kernel) and against the separate rmsnorm2 kernels (> 8 rows: two dependent launches of
+        // ~6 us per layer) the measured layer goes 37.0 -> 34.4 us at 2 rows, 39.4 -> 35.7 at 8, 66.5 -> 61.6 at 32; at 64 rows it is a draw (83.3 / 82.9: the
+        // 960 workgroups of wqkv each repeat the row statistics) and at 128 a loss (120 / 125), so larger chains keep the norm kernels.  The first norm of layer 0
+        // (token gather) and of the three control-add layers changes the stream before it is normed: those keep the prologue / kernel form.
+        cp.normx_max = normx_max; cp.normx_j4 = normx_j4; cp.staged_normx = !no_staged;
+        cp.normx = bg <= normx_max && D % 128 == 0 && D <= 2048 && !no_normx;      // D/32 and D/16 partials per row: multiples of 4, at most 128 (the fold's 16-byte loads)
+        // L2 run-ahead (round 6).  The per-XCD L2 survives a kernel boundary (experiments/xk_cache: a region the same XCD read one kernel earlier streams at L2 speed), and
+        // kernels that occupy a fraction of the 256 CUs carry HELPER workgroups that touch the weights of the kernels that follow, XCD by XCD (decode2_params.h CAR_PF_FIELDS):
+        //   RA_SMALL  chains of one m-block (BASELINE configs 2, 4, 5): attention (40-160 CUs) -> wo + w1|w3 of this layer, wo -> w2 of this layer, w2 -> wqkv of the next layer
+        //             (the last layer: the first 16 MB of the vocabulary projection), so that the HBM stream of a layer's 41 MB runs under its latency-bound kernels.
+        //             experiments/lat_probe, 2 rows, position 631: 35.1 -> 32.7 us per layer.
+        //   RA_NX     ONE chain of 17-normx_max rows (on-the-fly norm: few rmsnorm2 launches to ride on): wo (80-240 workgroups) hosts w1|w3 + w2, w2 hosts the next layer's wqkv;
+        //             the rmsnorm2 launches that remain host helpers as in RA_MID
+        //   RA_MID    ONE chain of more rows (BASELINE config 3): the rmsnorm2 launches in front of wqkv / w1|w3 / output are 4-48 workgroups; their helpers pull the weights of the
+        //             linears behind them into the XCDs' L2s (attention_norm -> wqkv; ffn_norm -> w1|w3 + w2; final norm -> 16 MB of the vocabulary projection)
+        if (n_cu >= 128 && !no_runahead) cp.runahead = bg <= 16 ? RA_SMALL : (bg != b ? RA_NONE : (bg <= normx_max ? RA_NX : RA_MID));
+        cp.kv_runahead = kv_runahead && cp.attn_variant == 162 && ((bg * Hn) & 7) == 0;
+    }
+    // ---- exact mode, three chains: the FIRST positions run as ONE chain.  Chains buy overlap of one chain's KV stream with the others' linears at the price of
+    // re-streaming the weights per chain and of smaller GEMMs; while the KV prefix is short there is little to overlap (profiles/r05_exact_probe_v5_positions.txt,
+    // 384 sequences, ms per step, 1 / 3 chains: position 120 8.47 / 9.25, 220 10.08 / 10.44, 370 13.19 / 12.62, 629 18.50 / 17.45, 1120 28.87 / 27.04).  The
+    // cross-over sits where a sequence's KV rows cost ~0.6 of its share of the linears: rows* = 0.087 · P / (8 · dim · n_layer) attended rows (177 for XL).  The
+    // host knows the position of every replay, so the loop is two captured graphs; the per-chain (pos, step) scalars are rewritten between them.  Chains are
+    // row ranges of the same buffers and every kernel is batch-invariant: the switch does not touch a token.
+    if (!fast && NG == 3 && mult == 1 && !k_chains && !no_early) {
+        const double P = (double)g.n_layer * (4.0 * D * D + 3.0 * (double)D * Fh) + (double)V * D;
+        const int rows_star = (int)(0.087 * P / (8.0 * D * g.n_layer));
+        const int attended0 = has_mask ? 24 : T;                       // attended prefix rows at the first decode step (left-padded captions: ~24 of 120 valid on average)
+        pl.n_early = std::min(rows_star - attended0 - skip, nsteps); if (pl.n_early < 8) pl.n_early = 0;
+        pl.ch[kEarlyChain].bg = b; plan_exact(pl.ch[kEarlyChain]);
+    }
+}
+
+// What the step builders read besides the plan and the weights: the shared buffers, the call's shapes and each chain's pointers and sampler.
 struct FastBufs { bf16_t *xn, *att, *mid, *q; float* logits; float* attn_part; float* ssq; };     // per-chain scratch (XP-packed activations; ssq: row sums of squares of the residual stream as per-tile partials [rows][dim/16])
-struct Grp { int b0, bg, nsplit, attn_variant, attn_lds_pad, attn_pgrid; int *pos, *step; FastBufs fb; SampleP sp; };
+struct ChainBind { int *pos, *step; FastBufs fb; SampleP sp; };
+struct StepBufs {
+    void *h, *xn, *qkv, *att, *mid; float* part; float* logits; int* cur;
+    int b, SA, n_tok; bool use_ctrl; float cs; const unsigned char* maskb; const int* jmin;      // SA: KV rows per (sequence, head) (exact mode: S_max)
+    ChainBind ch[9];                                 // as DecodePlan::ch
+};
 
 // bf16 fast path (decode2.hip): 7 kernels per layer — norm -> wqkv(+RoPE, KV write) -> attention -> wo(+residual) ->
 // norm -> w1|w3(+SwiGLU) -> w2(+residual); every linear streams the weights once for all rows of the chain.
 // `phase_ev` / `phase_dst` (multi-chain capture): right after this chain's FIRST wqkv the event is recorded and `phase_dst` (the next
 // chain's stream) is made to wait for it — the next chain enters the step half a layer late, so that its latency-bound linears run
 // under this chain's HBM-bound attention and vice versa (chains forked at the same node run in lockstep: both do their linears at the
-// same time, then both their attention, and nothing is hidden).  `prio`: the linears / norms raise their wave priority (s_setprio).
-static int enqueue_decode_step_fast(car_ctx* c, const StepBufs& sb, const Grp& gr, int b_total, int SA, int n_tok, bool use_ctrl,
-                                    float cs, const unsigned char* maskb, const int* jmin, hipStream_t st,
-                                    hipEvent_t phase_ev = nullptr, hipStream_t phase_dst = nullptr, int prio = 0) {
+// same time, then both their attention, and nothing is hidden).
+static int enqueue_decode_step_fast(car_ctx* c, const StepBufs& sb, const DecodePlan& pl, int ci, hipStream_t st, hipEvent_t phase_ev, hipStream_t phase_dst) {
     const car_config& g = c->cfg;
+    const ChainPlan& cp = pl.ch[ci]; const ChainBind& cb = sb.ch[ci]; const FastBufs& fb = cb.fb;
     const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, li = g.n_layer / 3, V = g.vocab_size, T = g.cls_token_num;
-    const int b = gr.bg, b0 = gr.b0, nsplit = gr.nsplit;
-    const FastBufs& fb = gr.fb;
-    const size_t kv_layer = (size_t)b_total * Hn * SA * 64, kv_off = (size_t)b0 * Hn * SA * 64;
+    const int b = cp.bg, b0 = cp.b0, nsplit = cp.nsplit, SA = sb.SA, n_tok = sb.n_tok, prio = pl.lin_prio;
+    const size_t kv_layer = (size_t)sb.b * Hn * SA * 64, kv_off = (size_t)b0 * Hn * SA * 64;
     bf16_t* h = (bf16_t*)sb.h + (size_t)b0 * D;
     const bool f8 = g.decode_weight_fp8 != 0;
-    int normx_max = 48; bool normx_j4 = false;
-    { const char* ev = CAR_KNOB("CAR_NORMX_MAX"); if (ev) normx_max = atoi(ev); ev = CAR_KNOB("CAR_NORMX_J4"); if (ev) normx_j4 = atoi(ev) != 0; }
     int nk = 0, bad_cfg = 0;
-    // L2 run-ahead (round 6; chains of one m-block: BASELINE configs 2, 4, 5).  The per-XCD L2 survives a kernel boundary (experiments/xk_cache: a region the same XCD
-    // read one kernel earlier streams at L2 speed), and three of a small layer's five kernels — attention, wo, w2 — occupy 40-160 of the 256 CUs.  They carry HELPER
-    // workgroups that touch the weights of the kernels that follow, XCD by XCD (decode2_params.h CAR_PF_FIELDS):
-    //     attention -> wo + w1|w3 of this layer,   wo -> w2 of this layer,   w2 -> wqkv of the next layer (the last layer: the first 16 MB of the vocabulary projection)
-    // so that the HBM stream of a layer's 41 MB runs under its latency-bound kernels.  experiments/lat_probe, 2 rows, position 631: 35.1 -> 32.7 us per layer.
-    const bool runahead = b <= 16 && c->n_cu >= 128 && !CAR_KNOB("CAR_NO_RUNAHEAD");
+    const bool ra_lin = cp.runahead == RA_SMALL || cp.runahead == RA_NX, ra_norm = cp.runahead == RA_NX || cp.runahead == RA_MID;      // helpers ride on the attention / linears, on the rmsnorm2 launches
     auto wimg = [&](const std::string& wname, const void*& ptr, unsigned& bytes, size_t cap = (size_t)24 << 20) {
         auto it = c->w.find(wname + (f8 ? "#pk8" : "#pk"));
         if (it == c->w.end()) { ptr = nullptr; bytes = 0; return; }
         ptr = it->second.p; bytes = (unsigned)std::min(it->second.bytes, cap);
     };
-    // chains of 17-48 rows (on-the-fly norm: no rmsnorm2 launches to ride on): wo (80-240 workgroups) hosts w1|w3 + w2, w2 hosts the next layer's wqkv
-    const bool runahead_nx = b > 16 && b <= normx_max && b == b_total && c->n_cu >= 128 && !CAR_KNOB("CAR_NO_RUNAHEAD");
-    auto helpers_for = [&](int main_wgs) -> int {      // helper workgroups beside `main_wgs` workgroups: fill the chip once, multiple of 8 (the helper's XCD arithmetic), at least 32
-        if (!(runahead || runahead_nx) || (main_wgs & 7)) return 0;
-        int h = ((c->n_cu - main_wgs) / 8) * 8;
-        if (h > 192) h = 192;
-        return h >= 32 ? h : 0;
+    auto helpers_for = [&](bool on, int main_wgs) -> int {      // helper workgroups beside `main_wgs` workgroups: fill the chip once, multiple of 8 (the helper's XCD arithmetic), at least 32, at most 192
+        if (!on || (main_wgs & 7)) return 0;
+        const int n = std::min(((c->n_cu - main_wgs) / 8) * 8, 192);
+        return n >= 32 ? n : 0;
     };
-    // Mid chains (17-191 rows as ONE chain: BASELINE config 3): the rmsnorm2 launches in front of wqkv / w1|w3 / output are 4-48 workgroups on a 256-CU chip; their
-    // helpers pull the weights of the linears behind them into the XCDs' L2s (attention_norm -> wqkv; ffn_norm -> w1|w3 + w2; final norm -> 16 MB of the vocabulary projection)
-    const bool runahead_mid = b > 16 && b == b_total && c->n_cu >= 128 && !CAR_KNOB("CAR_NO_RUNAHEAD");
-    auto norm_helpers = [&](Norm2P& np, const std::string& w0, const std::string& w1, size_t cap0 = (size_t)24 << 20) {
-        if (!runahead_mid) return;
-        const int main_wgs = (b + 3) / 4;
-        if (main_wgs & 7) return;
-        int h = ((c->n_cu - main_wgs) / 8) * 8; if (h > 192) h = 192; if (h < 32) return;
-        np.pf_wgs = h; wimg(w0, np.pf_p0, np.pf_b0, cap0); if (!w1.empty()) wimg(w1, np.pf_p1, np.pf_b1);
-    };
+    auto ctrl_at = [&](int l) { return sb.use_ctrl && l < g.n_layer && l % li == 0 && l / li < 3; };      // a control token is added in front of layer l
     // returns the number of sum-of-squares partials per row the kernel leaves in p.ssq_out (0 if it writes none)
     auto gemm = [&](const std::string& wname, const bf16_t* X, int N, int K, int epi, GemmDP gp_) -> int {
         GemmDP p = gp_;
@@ -67,121 +175,98 @@ static int enqueue_decode_step_fast(car_ctx* c, const StepBufs& sb, const Grp& g
         int cfg = car_pick_gemm_cfg(b, N, K, epi);
         // 49-64 rows behind an on-the-fly norm: ALL four m-blocks in one workgroup (J = 4), so the row statistics are folded once per weight tile instead of
         // once per (weight tile, m-block) — 240 workgroups of wqkv instead of 960, each re-reading the same 20 KB of partials (profiles/r04_lat_probe_v5_rows64.txt)
-        if (p.ssq_in && b > 48 && b <= 64 && normx_j4) cfg = ((epi == EPI_SWIGLU || N >= 6144) ? 200 : 100) + 40 + 1;
+        if (p.ssq_in && b > 48 && b <= 64 && cp.normx_j4) cfg = ((epi == EPI_SWIGLU || N >= 6144) ? 200 : 100) + 40 + 1;
         const int I = cfg / 100, J = (cfg / 10) % 10, Mb = (b + 15) / 16;
         p.w_nt = ((Mb + J - 1) / J == 1 ? 1 : 0) | (prio ? 2 : 0);      // bit 0: non-temporal weight stream, bit 1: raised wave priority
-        if (p.pf_wgs > 0) { p.pf_wgs = helpers_for((N / (16 * I)) * ((Mb + J - 1) / J)); if (p.pf_wgs > 160) p.pf_wgs = 160; }      // (the caller marks the kernels that host helpers)
+        if (p.pf_wgs > 0) p.pf_wgs = std::min(helpers_for(ra_lin, (N / (16 * I)) * ((Mb + J - 1) / J)), 160);      // (the caller marks the kernels that host helpers)
         if (p.ssq_out) p.ssq_ld = N / (16 * (I >= 2 ? 2 : 1));
-        if (car_launch_dec_gemm_cfg(&p, epi, cfg, st)) bad_cfg = cfg;
+        if (car_launch_dec_gemm_cfg_ex(&p, epi, cfg, cp.staged_normx, st)) bad_cfg = cfg;
         ++nk;
         return p.ssq_out ? p.ssq_ld : 0;
     };
     GemmDP z; memset(&z, 0, sizeof(z));
-    // tiny chains (<= 8 rows): the latency-bound regime (BASELINE configs 2, 4, 5).  The two RMSNorms of a layer and the final norm run
-    // in the prologue of the GEMM that consumes them (dec_gemm NORM variant), and the attention is ONE launch of 16-wave workgroups
-    // (no split-KV partials, no combine kernel): 5 dependent kernels per layer instead of 8.  Measured on MI355X with the layer loop of
-    // experiments/small_chain (profiles/r03_small_chain.txt, position 631, us per layer): 2 rows 40.2 -> 35.2, 4 rows 41.6 -> 35.7,
-    // 8 rows 47.8 -> 37.4 with 8-wave tiles (one row of the prologue norm per wave); from 12 rows up the fused prologue (every workgroup
-    // repeats the norm of all rows) no longer wins (44.1 either way at 12, 50.1 vs 49.4 at 16) and the separate norm kernels stay.
-    // The floor of this structure is the kernel boundary itself: 5 EMPTY kernels per layer cost 8.3 us.
-    const bool fuse_norm = b <= 8 && D <= 2048 && !CAR_KNOB("CAR_NO_SMALL_FUSE");
-    // chains of up to 48 rows (round 4, experiments/lat_probe: profiles/r04_lat_probe_v5_*): the RMSNorm in front of wqkv / w1|w3 / output is applied ON THE FLY.
-    // The RESID linear that produced the residual stream (wo, w2) leaves each row's sum of squares as per-tile partials; the consumer folds them into rstd
-    // and normalises the bf16 residual rows it loads as its X operand in registers (dec_gemm NORM == 2).  Against the prologue form (<= 8 rows: a barrier-
-    // separated norm in front of the main loop, 3.6-6.0 us of a 6-8 us kernel) and against the separate rmsnorm2 kernels (> 8 rows: two dependent launches of
-    // ~6 us per layer) the measured layer goes 37.0 -> 34.4 us at 2 rows, 39.4 -> 35.7 at 8, 66.5 -> 61.6 at 32; at 64 rows it is a draw (83.3 / 82.9: the
-    // 960 workgroups of wqkv each repeat the row statistics) and at 128 a loss (120 / 125), so larger chains keep the norm kernels.  The first norm of layer 0
-    // (token gather) and of the three control-add layers changes the stream before it is normed: those keep the prologue / kernel form.
-    const bool normx = b <= normx_max && D % 128 == 0 && D <= 2048 && fb.ssq != nullptr && !CAR_KNOB("CAR_NO_NORMX");      // D/32 and D/16 partials per row: multiples of 4, at most 128 (the fold's 16-byte loads)
     int ssq_np = 0;                                                   // partials per row currently valid in fb.ssq (0: none)
     bf16_t* hc = h;                                                  // the residual stream; ping-pongs with `halt` when a control token is added
     bf16_t* halt = (bf16_t*)sb.xn + (size_t)b0 * D;                  // (the prefill's xn buffer is idle during decode)
+    // a separate rmsnorm2 launch in front of layer l's wqkv (l >= 0: [token gather at layer 0] (+ control add at layers 0, n/3, 2n/3) -> h ; norm -> xn, packed) or of
+    // another linear (l < 0); its run-ahead helpers pull the weight images `pf0` (at most `cap0` bytes) and `pf1`
+    auto norm_kernel = [&](const std::string& wname, int l, const std::string& pf0, const std::string& pf1, size_t cap0 = (size_t)24 << 20) {
+        Norm2P np; memset(&np, 0, sizeof(np));
+        np.h_in = h; np.xn = fb.xn; np.w = (const bf16_t*)Wp(c, wname); np.D = D; np.eps = g.norm_eps; np.add = prio ? 2 : 0;
+        if (l == 0) { np.emb = (const bf16_t*)Wp(c, "tok_embeddings.weight"); np.idx = sb.cur + b0; np.h_out = h; }
+        if (l >= 0 && ctrl_at(l)) {
+            np.add |= 1; np.ctrl = (const bf16_t*)c->ctrl[l / li].p + (size_t)b0 * n_tok * D; np.pos = cb.pos; np.T = T; np.n_tok = n_tok; np.cs = sb.cs; np.h_out = h;
+        }
+        np.pf_wgs = helpers_for(ra_norm, (b + 3) / 4);
+        if (np.pf_wgs > 0) { wimg(pf0, np.pf_p0, np.pf_b0, cap0); if (!pf1.empty()) wimg(pf1, np.pf_p1, np.pf_b1); }
+        car_launch_rmsnorm2(&np, b, st); ++nk;
+    };
     auto normx_fields = [&](GemmDP& q, const std::string& wname) { q.nw = (const bf16_t*)Wp(c, wname); q.neps = g.norm_eps; q.nh_in = hc; q.ssq_in = fb.ssq; q.ssq_np = ssq_np; };
     auto norm_fields = [&](GemmDP& q, const std::string& wname, int l, bool first_of_layer) {
-        q.nw = (const bf16_t*)Wp(c, wname); q.neps = g.norm_eps; q.nh_in = hc; q.pos = gr.pos;
+        q.nw = (const bf16_t*)Wp(c, wname); q.neps = g.norm_eps; q.nh_in = hc; q.pos = cb.pos;
         if (first_of_layer && l == 0) { q.nemb = (const bf16_t*)Wp(c, "tok_embeddings.weight"); q.nidx = sb.cur + b0; q.nh_out = h; }
-        if (first_of_layer && use_ctrl && l % li == 0 && l / li < 3) {
-            q.nadd = 1; q.nctrl = (const bf16_t*)c->ctrl[l / li].p + (size_t)b0 * n_tok * D; q.nT = T; q.n_tok = n_tok; q.ncs = cs;
+        if (first_of_layer && ctrl_at(l)) {
+            q.nadd = 1; q.nctrl = (const bf16_t*)c->ctrl[l / li].p + (size_t)b0 * n_tok * D; q.nT = T; q.n_tok = n_tok; q.ncs = sb.cs;
             q.nh_out = l == 0 ? h : (hc == h ? halt : h);            // never in place: every workgroup re-reads the un-added stream
         }
+    };
+    // the norm in front of a linear: on the fly (valid partials in fb.ssq), in the GEMM's prologue, or its own launch
+    auto norm_for = [&](GemmDP& q, bool nx, const std::string& wname, int l, bool first_of_layer, const std::string& pf0, const std::string& pf1, size_t cap0 = (size_t)24 << 20) {
+        if (nx) normx_fields(q, wname);
+        else if (cp.fuse_norm) norm_fields(q, wname, l, first_of_layer);
+        else norm_kernel(wname, first_of_layer ? l : -1, pf0, pf1, cap0);
     };
     for (int l = 0; l < g.n_layer; ++l) {
         const std::string L = "layers." + std::to_string(l) + ".";
         const size_t kvb = g.kv_cache_fp8 ? 1 : 2;          // bytes per cached element (e4m3 / bf16)
         bf16_t* kc = (bf16_t*)((char*)c->kv.p + ((size_t)(2 * l) * kv_layer + kv_off) * kvb); bf16_t* vc = (bf16_t*)((char*)c->kv.p + ((size_t)(2 * l + 1) * kv_layer + kv_off) * kvb);
-        const bool special = l == 0 || (use_ctrl && l % li == 0 && l / li < 3);      // the stream changes (gather / control add) before this layer's first norm
-        const bool nx1 = normx && !special && ssq_np > 0;
-        if (!nx1 && !fuse_norm) {   // [token gather at layer 0] (+ control add at layers 0, n/3, 2n/3) -> h ; attention_norm -> xn (packed)
-            Norm2P np; memset(&np, 0, sizeof(np));
-            np.h_in = h; np.xn = fb.xn; np.w = (const bf16_t*)Wp(c, L + "attention_norm.weight"); np.D = D; np.eps = g.norm_eps; np.add = prio ? 2 : 0;
-            if (l == 0) { np.emb = (const bf16_t*)Wp(c, "tok_embeddings.weight"); np.idx = sb.cur + b0; np.h_out = h; }
-            if (use_ctrl && l % li == 0 && l / li < 3) {
-                np.add |= 1; np.ctrl = (const bf16_t*)c->ctrl[l / li].p + (size_t)b0 * n_tok * D; np.pos = gr.pos; np.T = T; np.n_tok = n_tok; np.cs = cs; np.h_out = h;
-            }
-            norm_helpers(np, L + "attention.wqkv.weight", "");
-            car_launch_rmsnorm2(&np, b, st); ++nk;
-        }
+        const bool special = l == 0 || ctrl_at(l);      // the stream changes (gather / control add) before this layer's first norm
+        const bool nx1 = cp.normx && !special && ssq_np > 0;
         {
-            GemmDP q = z; q.qout = fb.q; q.kc = kc; q.vc = vc; q.rope = c->rope; q.pos = gr.pos; q.H = Hn; q.SA = SA; q.dim = D; q.kv8 = g.kv_cache_fp8 ? 1 : 0;
-            if (nx1) normx_fields(q, L + "attention_norm.weight");
-            else if (fuse_norm) { norm_fields(q, L + "attention_norm.weight", l, true); }
+            GemmDP q = z; q.qout = fb.q; q.kc = kc; q.vc = vc; q.rope = c->rope; q.pos = cb.pos; q.H = Hn; q.SA = SA; q.dim = D; q.kv8 = g.kv_cache_fp8 ? 1 : 0;
+            norm_for(q, nx1, L + "attention_norm.weight", l, true, L + "attention.wqkv.weight", "");
             gemm(L + "attention.wqkv.weight", fb.xn, 3 * D, D, EPI_QKV, q);
-            if (!nx1 && fuse_norm && q.nh_out) hc = q.nh_out;
+            if (!nx1 && cp.fuse_norm && q.nh_out) hc = q.nh_out;
             if (l == 0 && phase_ev) { (void)hipEventRecord(phase_ev, st); (void)hipStreamWaitEvent(phase_dst, phase_ev, 0); }
         }
         {
             Attn2P ap; memset(&ap, 0, sizeof(ap));
-            ap.q = fb.q; ap.kc = kc; ap.vc = vc; ap.pos = gr.pos; ap.mask = maskb ? maskb + (size_t)b0 * T : nullptr; ap.jmin = jmin ? jmin + b0 : nullptr;
+            ap.q = fb.q; ap.kc = kc; ap.vc = vc; ap.pos = cb.pos; ap.mask = sb.maskb ? sb.maskb + (size_t)b0 * T : nullptr; ap.jmin = sb.jmin ? sb.jmin + b0 : nullptr;
             ap.out = fb.att; ap.part = fb.attn_part; ap.H = Hn; ap.SA = SA; ap.T = T; ap.dim = D; ap.nsplit = nsplit; ap.out_packed = 1; ap.kv8 = g.kv_cache_fp8 ? 1 : 0;
-            if (gr.attn_pgrid > 0 && nsplit == 1) { ap.n_seq = b; ap.pgrid = gr.attn_pgrid; }
-            if (gr.attn_variant == 162) {      // the small-batch kernel hosts the run-ahead for wo and w1|w3
-                ap.pf_wgs = helpers_for(b * Hn);
+            if (cp.attn_pgrid > 0 && nsplit == 1) { ap.n_seq = b; ap.pgrid = cp.attn_pgrid; }
+            if (cp.attn_variant == 162) {      // the small-batch kernel hosts the run-ahead for wo and w1|w3
+                ap.pf_wgs = helpers_for(ra_lin, b * Hn);
                 if (ap.pf_wgs > 0) { wimg(L + "attention.wo.weight", ap.pf_p0, ap.pf_b0); wimg(L + "feed_forward.w13.weight", ap.pf_p1, ap.pf_b1); }
             }
-            car_launch_dec_attn2_var(&ap, b, gr.attn_variant, gr.attn_lds_pad, st); nk += nsplit > 1 ? 2 : 1;
+            car_launch_dec_attn2_var(&ap, b, cp.attn_variant, cp.attn_lds_pad, st); nk += nsplit > 1 ? 2 : 1;
         }
-        { GemmDP q = z; q.h = hc; if (normx) q.ssq_out = fb.ssq;
-          if (runahead) { q.pf_wgs = 1; wimg(L + "feed_forward.w2.weight", q.pf_p0, q.pf_b0); }
-          else if (runahead_nx) { q.pf_wgs = 1; wimg(L + "feed_forward.w13.weight", q.pf_p0, q.pf_b0); wimg(L + "feed_forward.w2.weight", q.pf_p1, q.pf_b1); }
+        { GemmDP q = z; q.h = hc; if (cp.normx) q.ssq_out = fb.ssq;
+          if (cp.runahead == RA_SMALL) { q.pf_wgs = 1; wimg(L + "feed_forward.w2.weight", q.pf_p0, q.pf_b0); }
+          else if (cp.runahead == RA_NX) { q.pf_wgs = 1; wimg(L + "feed_forward.w13.weight", q.pf_p0, q.pf_b0); wimg(L + "feed_forward.w2.weight", q.pf_p1, q.pf_b1); }
           ssq_np = gemm(L + "attention.wo.weight", fb.att, D, D, EPI_RESID, q); }
-        const bool nx2 = normx && ssq_np > 0;
-        if (!nx2 && !fuse_norm) {
-            Norm2P np; memset(&np, 0, sizeof(np));
-            np.h_in = h; np.xn = fb.xn; np.w = (const bf16_t*)Wp(c, L + "ffn_norm.weight"); np.D = D; np.eps = g.norm_eps; np.add = prio ? 2 : 0;
-            norm_helpers(np, L + "feed_forward.w13.weight", L + "feed_forward.w2.weight");
-            car_launch_rmsnorm2(&np, b, st); ++nk;
-        }
         { GemmDP q = z; q.outp = fb.mid;
-          if (nx2) normx_fields(q, L + "ffn_norm.weight"); else if (fuse_norm) norm_fields(q, L + "ffn_norm.weight", l, false);
+          norm_for(q, cp.normx && ssq_np > 0, L + "ffn_norm.weight", l, false, L + "feed_forward.w13.weight", L + "feed_forward.w2.weight");
           gemm(L + "feed_forward.w13.weight", fb.xn, 2 * Fh, D, EPI_SWIGLU, q); }
         {   // w2 leaves the sums of squares for the next layer's first norm (or the final norm) unless that layer adds a control token first
-            const bool next_special = l + 1 < g.n_layer && use_ctrl && (l + 1) % li == 0 && (l + 1) / li < 3;
-            GemmDP q = z; q.h = hc; if (normx && !next_special) q.ssq_out = fb.ssq;
-            if (runahead || runahead_nx) {
+            GemmDP q = z; q.h = hc; if (cp.normx && !ctrl_at(l + 1)) q.ssq_out = fb.ssq;
+            if (ra_lin) {
                 q.pf_wgs = 1; wimg(l + 1 < g.n_layer ? "layers." + std::to_string(l + 1) + ".attention.wqkv.weight" : std::string("output.weight"), q.pf_p0, q.pf_b0, (size_t)16 << 20);
                 // the KV prefixes the next layer's attention will stream — MEASURED, OFF (development switch): the attention shrinks 6.5 -> 4.4 us at 2 rows, but w2 and the two
                 // boundaries behind the helpers grow by as much (32.4 vs 32.6 us per layer at position 631, 31.7 vs 32.4 at 200, 36.6 vs 39.7 at 8 rows; only past position
                 // ~1000 a gain: 34.8 -> 33.3): every kernel's span is already its own critical path, and a helper load that outlives it is paid at the boundary
-                if (l + 1 < g.n_layer && gr.attn_variant == 162 && ((b * Hn) & 7) == 0 && CAR_KNOB("CAR_KV_RUNAHEAD")) {
+                if (l + 1 < g.n_layer && cp.kv_runahead) {
                     q.pf_kc = (const char*)c->kv.p + ((size_t)(2 * (l + 1)) * kv_layer + kv_off) * kvb; q.pf_vc = (const char*)c->kv.p + ((size_t)(2 * (l + 1) + 1) * kv_layer + kv_off) * kvb;
-                    q.pf_pos = gr.pos; q.pf_items = b * Hn; q.pf_SA = SA; q.pf_kvb = (int)kvb;
+                    q.pf_pos = cb.pos; q.pf_items = b * Hn; q.pf_SA = SA; q.pf_kvb = (int)kvb;
                 }
             }
             ssq_np = gemm(L + "feed_forward.w2.weight", fb.mid, D, Fh, EPI_RESID, q);
         }
     }
-    const bool nx3 = normx && ssq_np > 0;
-    if (!nx3 && !fuse_norm) {
-        Norm2P np; memset(&np, 0, sizeof(np));
-        np.h_in = h; np.xn = fb.xn; np.w = (const bf16_t*)Wp(c, "norm.weight"); np.D = D; np.eps = g.norm_eps; np.add = prio ? 2 : 0;
-        norm_helpers(np, "output.weight", "", (size_t)16 << 20);
-        car_launch_rmsnorm2(&np, b, st); ++nk;
-    }
     { GemmDP q = z; q.outf = fb.logits;
-      if (nx3) normx_fields(q, "norm.weight"); else if (fuse_norm) norm_fields(q, "norm.weight", g.n_layer, false);
+      norm_for(q, cp.normx && ssq_np > 0, "norm.weight", g.n_layer, false, "output.weight", "", (size_t)16 << 20);
       gemm("output.weight", fb.xn, V, D, EPI_LOGITS, q); }
-    car_launch_advance(gr.pos, gr.step, st); ++nk;
-    SampleP sp = gr.sp; sp.logits = fb.logits; sp.logits_ks = 0; sp.round_bf16 = 0;
+    car_launch_advance(cb.pos, cb.step, st); ++nk;
+    SampleP sp = cb.sp; sp.logits = fb.logits; sp.logits_ks = 0; sp.round_bf16 = 0;
     car_launch_sample_greedy(&sp, st); ++nk;
     c->n_dec_kernels = nk;
     if (bad_cfg) FAIL(c, "decode GEMM: tile configuration %d rejected for this model's dimensions (b=%d, dim=%d, ffn=%d, vocab=%d)", bad_cfg, b, D, Fh, V);
@@ -194,22 +279,25 @@ static int enqueue_decode_step_fast(car_ctx* c, const StepBufs& sb, const Grp& g
 // linears behind a norm multiply the RAW residual rows by the image that carries the norm weight in its columns and scale by rstd in the epilogue (round 4
 // ran 8 kernels per layer: two rmsnorm launches and the split-KV combine).  Nothing here depends on the batch except the tile shape, which does not change
 // an output's arithmetic: a sequence decodes to the same bits alone and in a batch of 384.
-static int enqueue_decode_step(car_ctx* c, const StepBufs& sb, int b_total, int b0, int b, int S_max, int n_tok, int nsplit, bool use_ctrl,
-                               float cs, const SampleP& sp_chain, int* pos, int* step, const unsigned char* maskb, hipStream_t st,
-                               hipEvent_t phase_ev = nullptr, hipStream_t phase_dst = nullptr) {
-    // One chain = rows [b0, b0 + b) of the b_total decoded sequences (every buffer is row-major over the sequences, so a chain is a row offset).  With two
+static int enqueue_decode_step(car_ctx* c, const StepBufs& sb, const DecodePlan& pl, int ci, hipStream_t st, hipEvent_t phase_ev, hipStream_t phase_dst) {
+    // One chain = rows [b0, b0 + b) of the decoded sequences (every buffer is row-major over the sequences, so a chain is a row offset).  With two
     // chains the captured step has two branches: one chain's attention (HBM-bound) runs beside the other's linears (bound by the fp32 matrix pipe) — different
     // resources, unlike the bf16 step whose linears are latency-bound.  `phase_ev` / `phase_dst`: the next chain enters after this chain's first wqkv.
     const car_config& g = c->cfg; const int mode = c->mode; const size_t e = c->esz;
+    const ChainPlan& cp = pl.ch[ci]; const ChainBind& cb = sb.ch[ci];
     const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, li = g.n_layer / 3, V = g.vocab_size, T = g.cls_token_num;
-    const size_t kv_layer = (size_t)b_total * Hn * S_max * 64, kv_off = (size_t)b0 * Hn * S_max * 64;
+    const int b = cp.bg, b0 = cp.b0, nsplit = cp.nsplit, S_max = sb.SA, n_tok = sb.n_tok;
+    const size_t kv_layer = (size_t)sb.b * Hn * S_max * 64, kv_off = (size_t)b0 * Hn * S_max * 64;
     int nk = 0, bad = 0;
-    bool lin_prio = false; { const char* ev = CAR_KNOB("CAR_LINEAR_PRIO"); if (ev) lin_prio = atoi(ev) != 0; }
     auto gemm = [&](const std::string& wname, const void* X, long ldx, int N, int K, int epi, GemmFP q) {
         q.W = (const float*)Wp(c, wname + "#pk32"); q.X = (const float*)X; q.ldx = ldx; q.M = b; q.N = N; q.K = K;
-        int cfg = car_pick_gemm_f32_cfg2(b, N, K, epi, b_total / (b > 0 ? b : 1));
+        int cfg = car_pick_gemm_f32_cfg2(b, N, K, epi, sb.b / (b > 0 ? b : 1));
+        if (K % 128 == 0 && N % 64 == 0) {      // the shapes the LDS-tiled kernel takes: the A/B overrides of the plan
+            if (epi == FEPI_RESID) { if (pl.f32_resid_cfg != kNoOverride && b >= 64) cfg = pl.f32_resid_cfg; }
+            else if (N < 4096 && pl.f32_qkv_tiled_from != kNoOverride) cfg = b >= pl.f32_qkv_tiled_from ? 1212 : (b > 16 ? 22 : 21);
+        }
         const int J = cfg % 10, Mb = (b + 15) / 16;
-        q.w_nt = (cfg < 1000 && (Mb + J - 1) / J == 1 ? 1 : 0) | (lin_prio ? 2 : 0);
+        q.w_nt = (cfg < 1000 && (Mb + J - 1) / J == 1 ? 1 : 0) | (pl.lin_prio ? 2 : 0);
         if (!q.W || car_launch_dec_gemm_f32_cfg(&q, epi, cfg, st)) bad = cfg ? cfg : -1;
         ++nk;
     };
@@ -221,34 +309,30 @@ static int enqueue_decode_step(car_ctx* c, const StepBufs& sb, int b_total, int 
     for (int l = 0; l < g.n_layer; ++l) {
         const std::string L = "layers." + std::to_string(l) + ".";
         float* kc = (float*)off(c->kv.p, (size_t)(2 * l) * kv_layer + kv_off, e); float* vc = (float*)off(c->kv.p, (size_t)(2 * l + 1) * kv_layer + kv_off, e);
-        const bool ctrl_here = use_ctrl && l % li == 0 && l / li < 3;
+        const bool ctrl_here = sb.use_ctrl && l % li == 0 && l / li < 3;
         if (l == 0 || ctrl_here) {   // token gather (layer 0), control add (layers 0, n/3, 2n/3): the residual stream changes before its norm
             NormP np; memset(&np, 0, sizeof(np));
             np.h_in = h; np.h_out = h; np.xn = nullptr; np.D = D; np.eps = g.norm_eps;
             if (l == 0) { np.emb = Wp(c, "tok_embeddings.weight"); np.idx = sb.cur + b0; }
-            if (ctrl_here) { np.add_mode = 1; np.ctrl = off(c->ctrl[l / li].p, (size_t)b0 * n_tok * D, e); np.pos = pos; np.T = T; np.n_tok = n_tok; np.cs = cs; }
+            if (ctrl_here) { np.add_mode = 1; np.ctrl = off(c->ctrl[l / li].p, (size_t)b0 * n_tok * D, e); np.pos = cb.pos; np.T = T; np.n_tok = n_tok; np.cs = sb.cs; }
             car_launch_rmsnorm(mode, &np, b, st); ++nk;
         }
-        { GemmFP q = zn; q.qout = qbuf; q.kc = kc; q.vc = vc; q.rope = c->rope; q.pos = pos; q.H = Hn; q.S_max = S_max; q.dim = D;
+        { GemmFP q = zn; q.qout = qbuf; q.kc = kc; q.vc = vc; q.rope = c->rope; q.pos = cb.pos; q.H = Hn; q.S_max = S_max; q.dim = D;
           gemm(L + "attention.wqkv.weight", h, D, 3 * D, D, FEPI_QKV, q); }
         if (l == 0 && phase_ev) { (void)hipEventRecord(phase_ev, st); (void)hipStreamWaitEvent(phase_dst, phase_ev, 0); }
         {
             AttnFP ap; memset(&ap, 0, sizeof(ap));
-            ap.q = qbuf; ap.kc = kc; ap.vc = vc; ap.pos = pos; ap.mask = maskb ? maskb + (size_t)b0 * T : nullptr; ap.part = part; ap.out = att;
+            ap.q = qbuf; ap.kc = kc; ap.vc = vc; ap.pos = cb.pos; ap.mask = sb.maskb ? sb.maskb + (size_t)b0 * T : nullptr; ap.part = part; ap.out = att;
             ap.H = Hn; ap.S_max = S_max; ap.T = T; ap.dim = D; ap.nsplit_max = nsplit;
-            const bool fused = (long)Hn * b_total >= 2048 && nsplit <= 8;
-            // several chains: 12-wave attention workgroups (two per CU = 24 of its 32 wave slots), so that the other chain's linears find room beside it
-            int form = fused ? (b < b_total ? 3 : 1) : 0;
-            { const char* ev = CAR_KNOB("CAR_ATTN_F32_FORM"); if (ev && fused) form = atoi(ev); }
-            car_launch_dec_attn_f32_ex(&ap, b, form, st); nk += fused ? 1 : 2;
+            car_launch_dec_attn_f32_ex(&ap, b, cp.attn_variant, st); nk += cp.attn_variant ? 1 : 2;      // one fused launch, or the split kernel + combine
         }
         { GemmFP q = z; q.out = h; q.ldo = D; q.R = h; gemm(L + "attention.wo.weight", att, D, D, D, FEPI_RESID, q); }
         { GemmFP q = zn; q.out = mid; q.ldo = Fh; gemm(L + "feed_forward.w13.weight", h, D, 2 * Fh, D, FEPI_SWIGLU, q); }
         { GemmFP q = z; q.out = h; q.ldo = D; q.R = h; gemm(L + "feed_forward.w2.weight", mid, Fh, D, Fh, FEPI_RESID, q); }
     }
     { GemmFP q = zn; q.out = logits; q.ldo = V; gemm("output.weight", h, D, V, D, FEPI_PLAIN, q); }      // final norm on the fly; fp32 logits (exact mode has no bf16 round)
-    car_launch_advance(pos, step, st); ++nk;      // pos = T+i+1 consumed next step; step indexes the token being sampled
-    SampleP sp = sp_chain; sp.logits = logits; sp.step_ptr = step; car_launch_sample_greedy(&sp, st); ++nk;
+    car_launch_advance(cb.pos, cb.step, st); ++nk;      // pos = T+i+1 consumed next step; step indexes the token being sampled
+    SampleP sp = cb.sp; sp.logits = logits; sp.step_ptr = cb.step; car_launch_sample_greedy(&sp, st); ++nk;
     c->n_dec_kernels = nk;
     if (bad) FAIL(c, "exact-mode decode GEMM: tile configuration %d rejected (b=%d, dim=%d, ffn=%d, vocab=%d: N %% 32 and K %% 16 must be 0)", bad, b, D, Fh, V);
     return 0;
@@ -309,20 +393,12 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     // (so every group is a self-contained chain for the decode loop), plain image order otherwise.  NG = 1 reproduces the
     // reference layout [cond 0..B-1 | uncond 0..B-1] (generate.py:158-163).
     const bool fast = mode == CAR_BF16;
-    const int mult = use_cfg ? 2 : 1;
-    // two chains from 192 sequences up: each chain's GEMMs stream the weights once for <= 128+ rows, and one chain's HBM-bound
-    // attention runs beside the other's latency-bound GEMMs (profiles/r02_decode_chain_sweep.txt)
-    // (exact mode, round 4: the same cut — its linears are bound by the fp32 matrix pipe and its attention by HBM, so the two chains overlap DIFFERENT resources;
-    //  the rows of a chain are computed exactly as in any other batch, so the cut does not touch the mode's batch invariance)
-    int NG = b >= 192 ? 2 : 1;
-    // exact mode, round 5 (profiles/r05_exact_probe_*.txt, 384 sequences, mean position, ms per step): 1 chain 18.50, 2 chains 18.10, 3 chains 17.42, 4 chains
-    // 19.24, 6 chains 21.96.  The attention runs as 12-wave workgroups (decode_f32.hip: 24 of a CU's 32 wave slots), so the other chains' linears are resident
-    // beside it; a chain's four linears have to finish while the OTHER chains stream their KV, and with three chains that window is two attentions long.
-    if (!fast && b >= 288) NG = 3;
-    { const char* ev = CAR_KNOB("CAR_CHAINS"); if (ev) { int v = atoi(ev); if (v >= 1 && v <= 8 && B / v >= 2) NG = v; } }
-    if (CAR_KNOB("CAR_SINGLE_CHAIN") || NG > B) NG = 1;
-    int img0[9];
-    for (int gi = 0; gi <= NG; ++gi) img0[gi] = (int)((long)B * gi / NG);
+    // profiling aid (tools/pmc_workload.py): start the decode loop `skip` positions late so that a handful of steps under
+    // counter collection see a long KV prefix.  The skipped cache rows hold zeros / stale rows: tokens are meaningless.
+    { int skip = 0; const char* ev = CAR_KNOB("CAR_DEBUG_SKIP_STEPS"); if (ev) { skip = atoi(ev); if (skip < 0 || skip > n_new - 2) skip = 0; } c->dbg_skip = skip; }
+    const int nsteps = n_new - 1 - c->dbg_skip;
+    DecodePlan pl; plan_decode(pl, g, mode, c->n_cu, B, use_cfg, S_max, nsteps, c->dbg_skip, emb_mask != nullptr);      // the decode loop's schedule (chains included), decided once
+    const int NG = pl.NG, mult = pl.mult; const int* img0 = pl.img0;
     std::vector<int> row_img((size_t)b), row_unc((size_t)b);
     for (int gi = 0; gi < NG; ++gi) {
         const int ng = img0[gi + 1] - img0[gi], base = mult * img0[gi];
@@ -354,8 +430,7 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     // which a row's softmax partial sums are folded, so a sequence decodes to the same bits in a batch of 1 and in a batch of 384 (every other
     // exact-mode kernel sums one fixed-order fp32 chain per output): tests/test_parity_gpu.py::test_exact_mode_is_batch_invariant,
     // bench.py --precision fp32 (row 0 = the XL golden).
-    int nsplit = fast ? 1 : (S_max + AF_SPLIT - 1) / AF_SPLIT;
-    if (fast) { const int wg = b * Hn; while (wg * nsplit < 1024 && nsplit < 16) nsplit *= 2; }
+    const int nsplit = fast ? attn_splits(b * Hn) : pl.ch[0].nsplit;
     NEED(c, c->ws[10], (size_t)b * Hn * nsplit * 66 * 4);                     // split-KV partials
     NEED(c, c->ws[11], (size_t)B * (use_control ? n_tok : 1) * D * e);        // condition_mlp output / mlp mid
     // device scalars: [16 ints: (pos, step) of up to 8 chains] [cur_tok: b ints] [jmin: b ints] [jmin_min: 4 ints] [SampleDyn, 16-byte aligned]
@@ -423,14 +498,8 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     }
     const long rowsW = (long)b * Tv;                                           // rows the prefill computes (rowsP = b * T sized the buffers)
     const int Tpw = (int)rup(Tv, 32);
-    {
-        // profiling aid (tools/pmc_workload.py): start the decode loop `skip` positions late so that a handful of steps under
-        // counter collection see a long KV prefix.  The skipped cache rows hold zeros / stale rows: tokens are meaningless.
-        int skip = 0; { const char* ev = CAR_KNOB("CAR_DEBUG_SKIP_STEPS"); if (ev) { skip = atoi(ev); if (skip < 0 || skip > n_new - 2) skip = 0; } }
-        c->dbg_skip = skip;
-        for (int i = 0; i < 8; ++i) { c->h_init[2 * i] = T + skip; c->h_init[2 * i + 1] = skip; }    // (pos, step) per chain: after prefill the first decode step runs at input_pos = T, sampling token index 1
-        car_launch_set_pos_step(pos, c->h_init[0], c->h_init[1], st);
-    }
+    for (int i = 0; i < 8; ++i) { c->h_init[2 * i] = T + c->dbg_skip; c->h_init[2 * i + 1] = c->dbg_skip; }    // (pos, step) per chain: after prefill the first decode step runs at input_pos = T, sampling token index 1 (+ the profiling skip)
+    car_launch_set_pos_step(pos, c->h_init[0], c->h_init[1], st);
 
     // ---- D. text prefix embed: cls_embedding.cap_proj (gpt_t2i.py:435), uncond rows = uncond_embedding (generate.py:157)
     void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *P = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *att = c->ws[8].p;
@@ -534,146 +603,77 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     HIPCHK(c, hipEventRecord(c->ev_t1, st));
 
     // ---- F/G. decode loop: one captured step, replayed n_new-1 times (pos/step/token live on the device)
-    StepBufs sb;
-    sb.h = h; sb.xn = xn; sb.qkv = qkv; sb.att = att; sb.mid = mid; sb.mid2 = off(mid, (size_t)b * Fh, e);
-    sb.part = (float*)c->ws[10].p; sb.logits = logits; sb.pos = pos; sb.step = step; sb.cur = cur;
-    const int nsteps = n_new - 1 - c->dbg_skip;
+    StepBufs sb; memset(&sb, 0, sizeof(sb));
+    sb.h = h; sb.xn = xn; sb.qkv = qkv; sb.att = att; sb.mid = mid; sb.part = (float*)c->ws[10].p; sb.logits = logits; sb.cur = cur;
+    sb.b = b; sb.SA = SA; sb.n_tok = n_tok; sb.use_ctrl = use_control != 0; sb.cs = cs;
+    sb.maskb = emb_mask ? (const unsigned char*)c->maskb.p : nullptr; sb.jmin = emb_mask ? jmin : nullptr;      // no text-pad mask: nothing to test per position
     c->stats.graph_used = 0;
-    Grp grp[8]; memset(grp, 0, sizeof(grp));
+    for (int gi = 0; gi < NG; ++gi) {      // scal layout: (pos, step) x 8 chains, then cur_tok[b], then jmin[b]
+        ChainBind& cb = sb.ch[gi];
+        cb.pos = pos + 2 * gi; cb.step = step + 2 * gi; cb.sp = group_sampler(gi); cb.sp.step_ptr = cb.step;      // (sp.logits: set per launch to the chain's logits)
+    }
+    { ChainBind& cb = sb.ch[kEarlyChain]; cb.pos = pos; cb.step = step; cb.sp = spp; }      // the early one-chain schedule of exact mode: all rows
     if (fast) {
         // per-chain scratch from one arena: XP-packed xn / att [Mb*16, D], mid [Mb*16, Fh], q [bg, D] (bf16); logits [bg, V],
-        // split-KV partials (fp32).  Every slice is a multiple of 16 bytes.
-        size_t tot = 0; size_t sizes[8][7];
-        for (int gi = 0; gi < NG; ++gi) {
-            Grp& gr = grp[gi];
-            gr.b0 = mult * img0[gi]; gr.bg = mult * (img0[gi + 1] - img0[gi]);
-            const int bg = gr.bg; const size_t M16 = rup((size_t)bg, 16);
-            gr.nsplit = 1; { const int wg = bg * Hn; while (wg * gr.nsplit < 1024 && gr.nsplit < 16) gr.nsplit *= 2; }
-            // a handful of sequences (<= 240 (sequence, head) pairs = 12 XL sequences): ONE launch of 16-wave workgroups instead of split-KV + combine —
-            // one dependent kernel less per layer.  tools/small_ab.py on MI355X (XL, 1024 tokens, ms per step, same process): 2 rows 1.548 -> 1.406,
-            // 8 rows 1.611 -> 1.465, 12 rows 1.887 -> 1.725; at 16 rows the split form wins again (1.890 vs 1.923)  [profiles/r03_small_ab.txt]
-            // (round 6: with dec_attn2s — two blocks in flight per wave — the one-launch form wins up to 24 XL sequences: 38.8 -> 38.1 us per layer at 16 rows, 47.5 -> 45.9 at 20,
-            //  48.4 -> 46.9 at 24, tools/mid_ab.py with CAR_ONE_LAUNCH_MAX; 480 sixteen-wave workgroups still fit the chip in one round)
-            int one_max = T <= 512 ? 480 : 240; { const char* ev = CAR_KNOB("CAR_ONE_LAUNCH_MAX"); if (ev) one_max = atoi(ev); }
-            const bool one_launch = (long)bg * Hn <= one_max && !CAR_KNOB("CAR_ATTN_SPLIT_SMALL");
-            if (one_launch) gr.nsplit = 1;
-            { const char* ev = CAR_KNOB("CAR_ATTN_NSPLIT"); if (ev) { const int v = atoi(ev); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) gr.nsplit = v; } }   // A/B knob: shorter attention workgroups
-            // attention variant (decode2.hip; profiles/r02_kbench_*): 4 waves per (sequence, head) from 128 sequences up, 2 below; 16 in the one-launch small form
-            // (round 6: the one-launch form is dec_attn2s_kernel, variant 162 — two blocks in flight per wave, bit-identical to 160; it needs T <= 512 and the jmin table)
-            gr.attn_variant = (one_launch && gr.nsplit == 1) ? ((T <= 512 && !CAR_KNOB("CAR_ATTN_OLD_SMALL")) ? 162 : 160) : ((gr.nsplit == 1 && bg < 128) ? 20 : 40); gr.attn_lds_pad = 0;
-            { const char* ev = CAR_KNOB("CAR_ATTN_VARIANT"); if (ev) gr.attn_variant = atoi(ev); ev = CAR_KNOB("CAR_ATTN_LDS_PAD"); if (ev) gr.attn_lds_pad = atoi(ev); }
-            // persistent attention grid: R resident workgroups per CU walk the (sequence, head) items in equal shares
-            gr.attn_pgrid = 0;
-            { const char* ev = CAR_KNOB("CAR_ATTN_PERSIST"); const int R = ev ? atoi(ev) : 0;
-              if (R > 0 && R <= 16 && gr.nsplit == 1) { const long items = (long)bg * Hn, cap = (long)c->n_cu * R;
-                  if (items > cap) { const long per = (items + cap - 1) / cap; gr.attn_pgrid = (int)((items + per - 1) / per); } } }
-            sizes[gi][0] = M16 * D * 2; sizes[gi][1] = M16 * D * 2; sizes[gi][2] = M16 * Fh * 2; sizes[gi][3] = rup((size_t)bg * D * 2, 16);
-            sizes[gi][4] = (size_t)bg * V * 4; sizes[gi][5] = rup((size_t)bg * Hn * gr.nsplit * 66 * 4, 16); sizes[gi][6] = rup(M16 * (size_t)(D / 16) * 4, 16);
-            for (int k = 0; k < 7; ++k) tot += sizes[gi][k];
-        }
-        NEED(c, c->dec_parts, tot);
-        char* pbase = (char*)c->dec_parts.p;
-        for (int gi = 0; gi < NG; ++gi) {
-            Grp& gr = grp[gi]; FastBufs& f = gr.fb;
-            f.xn = (bf16_t*)pbase; pbase += sizes[gi][0]; f.att = (bf16_t*)pbase; pbase += sizes[gi][1]; f.mid = (bf16_t*)pbase; pbase += sizes[gi][2];
-            f.q = (bf16_t*)pbase; pbase += sizes[gi][3]; f.logits = (float*)pbase; pbase += sizes[gi][4]; f.attn_part = (float*)pbase; pbase += sizes[gi][5]; f.ssq = (float*)pbase; pbase += sizes[gi][6];
-            gr.pos = pos + 2 * gi; gr.step = step + 2 * gi;        // scal layout: (pos, step) x 8 chains, then cur_tok[b], then jmin[b]
-            gr.sp = group_sampler(gi); gr.sp.step_ptr = gr.step;
-            gr.sp.logits = nullptr;     // set per launch to the chain's logits
-        }
+        // split-KV partials (fp32), sum-of-squares partials.  Every slice is a multiple of 16 bytes.
+        auto carve = [&](uintptr_t base) -> size_t {      // lays the chains' slices out from `base`; returns their total size
+            size_t o = 0;
+            auto take = [&](size_t bytes) { void* p = (void*)(base + o); o += bytes; return p; };
+            for (int gi = 0; gi < NG; ++gi) {
+                const size_t bg = (size_t)pl.ch[gi].bg, M16 = rup(bg, 16); FastBufs& f = sb.ch[gi].fb;
+                f.xn = (bf16_t*)take(M16 * D * 2); f.att = (bf16_t*)take(M16 * D * 2); f.mid = (bf16_t*)take(M16 * Fh * 2); f.q = (bf16_t*)take(rup(bg * D * 2, 16));
+                f.logits = (float*)take(bg * V * 4); f.attn_part = (float*)take(rup(bg * Hn * pl.ch[gi].nsplit * 66 * 4, 16)); f.ssq = (float*)take(rup(M16 * (size_t)(D / 16) * 4, 16));
+            }
+            return o;
+        };
+        NEED(c, c->dec_parts, carve(0));
+        carve((uintptr_t)c->dec_parts.p);
     }
-    if (!fast) {       // exact mode: a chain is a row range of the shared row-major buffers
-        for (int gi = 0; gi < NG; ++gi) {
-            Grp& gr = grp[gi];
-            gr.b0 = mult * img0[gi]; gr.bg = mult * (img0[gi + 1] - img0[gi]); gr.nsplit = nsplit;
-            gr.pos = pos + 2 * gi; gr.step = step + 2 * gi;
-            gr.sp = group_sampler(gi); gr.sp.step_ptr = gr.step;
-        }
-    }
-    const unsigned char* fmask = emb_mask ? (const unsigned char*)c->maskb.p : nullptr;      // no text-pad mask: nothing to test per position
-    const int* fjmin = emb_mask ? jmin : nullptr;
-    // ---- decode-loop schedule knobs (fast mode), all OFF by default: the MI355X sweeps of tools/overlap_sweep.py found none of them worth a
-    // per cent (profiles/r02_overlap_sweep_v1..v3, DESIGN.md §4 — a linear beside the bandwidth-saturating attention makes no progress whatever
-    // the schedule); they stay as A/B switches, and tests/test_parity_gpu.py pins that none of them changes a token.
-    //   phase offset : with >= 2 chains, chain g+1 enters the step right after chain g's first wqkv (see enqueue_decode_step_fast)
-    //   graph steps  : consecutive tokens captured per graph replay — the chains free-run across them (one fork / join and one phase
-    //                  offset per `gsteps` tokens instead of per token); the remainder runs on a single-step graph
-    //   linear prio  : s_setprio on the linears / norms
-    int phase = fast ? 0 : 1, gsteps = 1, lin_prio = 0;      // exact mode: the second chain enters half a layer late, so that attention meets linears, not attention
-    { const char* ev = CAR_KNOB("CAR_PHASE_OFFSET"); if (ev) phase = atoi(ev) != 0; }
-    if (fast) {
-        const char* ev;
-        ev = CAR_KNOB("CAR_GRAPH_STEPS"); if (ev) { const int v = atoi(ev); if (v >= 1 && v <= 64) gsteps = v; }
-        ev = CAR_KNOB("CAR_LINEAR_PRIO"); if (ev) lin_prio = atoi(ev) != 0;
-    }
-    if (NG < 2) phase = 0;
-    // ---- exact mode, three chains: the FIRST positions run as ONE chain.  Chains buy overlap of one chain's KV stream with the others' linears at the price of
-    // re-streaming the weights per chain and of smaller GEMMs; while the KV prefix is short there is little to overlap (profiles/r05_exact_probe_v5_positions.txt,
-    // 384 sequences, ms per step, 1 / 3 chains: position 120 8.47 / 9.25, 220 10.08 / 10.44, 370 13.19 / 12.62, 629 18.50 / 17.45, 1120 28.87 / 27.04).  The
-    // cross-over sits where a sequence's KV rows cost ~0.6 of its share of the linears: rows* = 0.087 · P / (8 · dim · n_layer) attended rows (177 for XL).  The
-    // host knows the position of every replay, so the loop is two captured graphs; the per-chain (pos, step) scalars are rewritten between them.  Chains are
-    // row ranges of the same buffers and every kernel is batch-invariant: the switch does not touch a token.
-    int n_early = 0;
-    Grp grpE[1]; memset(grpE, 0, sizeof(grpE));
-    if (!fast && NG == 3 && mult == 1 && !CAR_KNOB("CAR_CHAINS") && !CAR_KNOB("CAR_NO_EARLY_CHAIN")) {
-        const double P = (double)g.n_layer * (4.0 * D * D + 3.0 * (double)D * Fh) + (double)V * D;
-        const int rows_star = (int)(0.087 * P / (8.0 * D * g.n_layer));
-        const int attended0 = emb_mask ? 24 : T;                       // attended prefix rows at the first decode step (left-padded captions: ~24 of 120 valid on average)
-        n_early = rows_star - attended0 - c->dbg_skip;
-        if (n_early > nsteps) n_early = nsteps;
-        if (n_early < 8) n_early = 0;
-        Grp& ge = grpE[0];
-        ge.b0 = 0; ge.bg = b; ge.nsplit = nsplit; ge.pos = pos; ge.step = step;
-        ge.sp = spp; ge.sp.step_ptr = step;
-    }
-    int NGc = NG, phasec = phase; Grp* grpc = grp;      // the schedule being enqueued / captured (main: NG chains; early: one chain)
-    bool capturing = false;
-    int step_rc = 0;
-    auto step_one = [&](int gi, hipStream_t sg, hipEvent_t pev, hipStream_t pdst) {
-        if (fast) return enqueue_decode_step_fast(c, sb, grpc[gi], b, SA, n_tok, use_control != 0, cs, fmask, fjmin, sg, pev, pdst, lin_prio);
-        return enqueue_decode_step(c, sb, b, grpc[gi].b0, grpc[gi].bg, S_max, n_tok, nsplit, use_control != 0, cs, grpc[gi].sp, grpc[gi].pos, grpc[gi].step, fmask, sg, pev, pdst);
-    };
-    auto enqueue_steps = [&](int k) {      // k consecutive decode steps of every chain
-        const int NG = NGc, phase = phasec;
-        if (NG >= 2 && capturing) {         // the chains are parallel branches of the captured graph
+    bool capturing = false; int step_rc = 0;
+    const auto step_one = fast ? enqueue_decode_step_fast : enqueue_decode_step;
+    auto enqueue_steps = [&](int k, bool early) {      // k consecutive decode steps of every chain of the main schedule, or of the one chain of the early schedule
+        const int c0 = early ? kEarlyChain : 0, n = early ? 1 : NG, phase = early ? 0 : pl.phase;
+        if (n >= 2 && capturing) {         // the chains are parallel branches of the captured graph
             if (!phase) {
                 (void)hipEventRecord(c->ev_fork, st);
-                for (int gi = 1; gi < NG; ++gi) (void)hipStreamWaitEvent(c->streamx[gi - 1], c->ev_fork, 0);
+                for (int gi = 1; gi < n; ++gi) (void)hipStreamWaitEvent(c->streamx[gi - 1], c->ev_fork, 0);
             }
-            for (int gi = 0; gi < NG; ++gi) {
+            for (int gi = 0; gi < n; ++gi) {
                 hipStream_t sg = gi == 0 ? st : c->streamx[gi - 1];
                 for (int s = 0; s < k; ++s) {
-                    const bool hand = phase && s == 0 && gi + 1 < NG;      // chain gi+1's stream joins the capture through this event
-                    step_rc |= step_one(gi, sg, hand ? c->ev_phase[gi] : nullptr, hand ? c->streamx[gi] : nullptr);
+                    const bool hand = phase && s == 0 && gi + 1 < n;      // chain gi+1's stream joins the capture through this event
+                    step_rc |= step_one(c, sb, pl, c0 + gi, sg, hand ? c->ev_phase[gi] : nullptr, hand ? c->streamx[gi] : nullptr);
                 }
                 if (gi > 0) { (void)hipEventRecord(c->ev_joinx[gi - 1], sg); (void)hipStreamWaitEvent(st, c->ev_joinx[gi - 1], 0); }
             }
         } else {
             for (int s = 0; s < k; ++s)
-                for (int gi = 0; gi < NG; ++gi) step_rc |= step_one(gi, st, nullptr, nullptr);
+                for (int gi = 0; gi < n; ++gi) step_rc |= step_one(c, sb, pl, c0 + gi, st, nullptr, nullptr);
         }
-        c->n_dec_kernels *= NG;             // kernel nodes of ONE step over all chains
+        c->n_dec_kernels *= n;             // kernel nodes of ONE step over all chains
     };
     if (nsteps > 0) {
-        char keyb[640];
-        // every scalar and pointer that the captured kernels bake in (n_new: the sampler's row stride and per-chain offsets)
-        snprintf(keyb, sizeof(keyb), "%d|%d|%d|%d|%d|%d|%d|%p|%p|%p|%p|%p|%p|%g|%g|%d|%d|%d|%p|%p", b, B, S_max, n_new, n_tok, nsplit, (int)use_control, c->kv.p, h, logits,
-                 c->ctrl[0].p, c->maskb.p, c->dec_parts.p ? c->dec_parts.p : c->ws[10].p, (double)cs, (double)sp->cfg_scale, sp->cfg_interval, NG, emb_mask ? 1 : 0,
-                 (const void*)forced_tokens, (void*)logits_out);
-        { char kb2[240]; snprintf(kb2, sizeof(kb2), "|%d|gen%llu|%p|%p|%p|%p|%d|%d|%d|%d|%d|%d", sp->sample_logits, g_alloc_gen, xn, att, mid, c->scal.p, grp[0].attn_variant, grp[0].attn_lds_pad,
-                                  grp[0].nsplit, phase, lin_prio, grp[0].attn_pgrid + 100000 * ((CAR_KNOB("CAR_NO_NORMX") ? 1 : 0) + (CAR_KNOB("CAR_NO_SMALL_FUSE") ? 2 : 0) + (CAR_KNOB("CAR_NO_RUNAHEAD") ? 4 : 0) + (CAR_KNOB("CAR_NO_STAGED_NORMX") ? 8 : 0) + (CAR_KNOB("CAR_KV_RUNAHEAD") ? 16 : 0)) + 1000000 * (CAR_KNOB("CAR_ONE_LAUNCH_MAX") ? atoi(CAR_KNOB("CAR_ONE_LAUNCH_MAX")) : 0));
-          strncat(keyb, kb2, sizeof(keyb) - strlen(keyb) - 1); }
-        { const char* k1 = CAR_KNOB("CAR_ATTN_F32_FORM"); const char* k2 = CAR_KNOB("CAR_LINEAR_PRIO"); const char* k3 = CAR_KNOB("CAR_NORMX_MAX"); const char* k4 = CAR_KNOB("CAR_NORMX_J4"); char kb3[64]; snprintf(kb3, sizeof(kb3), "|x%s|%s|%s|%s", k1 ? k1 : "-", k2 ? k2 : "-", k3 ? k3 : "-", k4 ? k4 : "-"); strncat(keyb, kb3, sizeof(keyb) - strlen(keyb) - 1); }
-        const std::string key(keyb);
-        const bool no_graph = CAR_KNOB("CAR_NO_GRAPH") != nullptr;      // profiling aid: eager launches (PMC collection cannot follow graph replays)
+        // The graph-cache key: the bytes of the plan and of the shapes and raw pointers that the capture bakes in (n_new: the sampler's row stride and per-chain
+        // offsets).  INVARIANT: whatever the step builders read comes from the plan, from a field keyed here, or from the weights — the plan is the schedule and
+        // the key, so a switch cannot change the captured kernels without changing the key.
+        struct GraphShapes {
+            int b, B, S_max, n_new, n_tok, nsplit, use_control, has_mask, cfg_interval, sample_logits; float cs, cfg_scale; unsigned long long alloc_gen;
+            const void *kv, *h, *xn, *att, *mid, *logits, *ctrl0, *maskb, *parts, *scal, *forced, *logits_out;
+        } gs;
+        memset(&gs, 0, sizeof(gs));      // (as plan_decode does for the plan: the padding is part of the key)
+        gs.b = b; gs.B = B; gs.S_max = S_max; gs.n_new = n_new; gs.n_tok = n_tok; gs.nsplit = nsplit; gs.use_control = use_control; gs.has_mask = emb_mask ? 1 : 0;
+        gs.cfg_interval = sp->cfg_interval; gs.sample_logits = sp->sample_logits; gs.cs = cs; gs.cfg_scale = sp->cfg_scale; gs.alloc_gen = g_alloc_gen;
+        gs.kv = c->kv.p; gs.h = h; gs.xn = xn; gs.att = att; gs.mid = mid; gs.logits = logits; gs.ctrl0 = c->ctrl[0].p; gs.maskb = c->maskb.p;
+        gs.parts = c->dec_parts.p ? c->dec_parts.p : c->ws[10].p; gs.scal = c->scal.p; gs.forced = forced_tokens; gs.logits_out = logits_out;
+        std::string key((const char*)&pl, sizeof(pl)); key.append((const char*)&gs, sizeof(gs));
         // capture `k` steps into `ex` unless the cached exec already holds exactly this configuration
-        auto get_exec = [&](hipGraphExec_t& ex, std::string& exkey, int k, const char* tag = "") -> bool {
-            const std::string kk = key + "|k" + std::to_string(k) + tag;
+        auto get_exec = [&](hipGraphExec_t& ex, std::string& exkey, int k, bool early = false) -> bool {
+            const std::string kk = key + "|k" + std::to_string(k) + (early ? "|early" : "");
             if (ex && exkey == kk) return true;
             if (ex) { (void)hipGraphExecDestroy(ex); ex = nullptr; exkey.clear(); }
             hipGraph_t graph = nullptr;
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return false; }
-            capturing = true; enqueue_steps(k); capturing = false;
+            capturing = true; enqueue_steps(k, early); capturing = false;
             bool ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph != nullptr;
             if (!ok) (void)hipGetLastError();
             // (per-node priorities were tried — attention low, linears high: hipGraphKernelNodeSetAttribute(hipKernelNodeAttributePriority) is
@@ -683,13 +683,12 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
             if (ok) exkey = kk;
             return ok;
         };
-        const int nmain = nsteps - n_early;
+        const int n_early = pl.n_early, gsteps = pl.gsteps, nmain = nsteps - n_early;
         const int nrep = nmain / gsteps, nrem = nmain % gsteps;
-        bool graph_ok = !no_graph;
-        auto early = [&](bool on) { if (on) { NGc = 1; phasec = 0; grpc = grpE; } else { NGc = NG; phasec = phase; grpc = grp; } };
+        bool graph_ok = !pl.no_graph;
         // the scalars of ALL chains at the switch: (pos, step) after n_early steps
         for (int i = 0; i < 8; ++i) { c->h_init2[2 * i] = c->h_init[0] + n_early; c->h_init2[2 * i + 1] = c->h_init[1] + n_early; }
-        if (graph_ok && n_early > 0) { early(true); graph_ok = get_exec(c->gexec1, c->gkey1, 1, "|early"); early(false); }      // (exact mode: gexec1 is free, gsteps == 1)
+        if (graph_ok && n_early > 0) graph_ok = get_exec(c->gexec1, c->gkey1, 1, true);      // (exact mode: gexec1 is free, gsteps == 1)
         if (graph_ok && nrep > 0) graph_ok = get_exec(c->gexec, c->gkey, gsteps);
         if (graph_ok && nrem > 0) graph_ok = get_exec(gsteps > 1 ? c->gexec1 : c->gexec, gsteps > 1 ? c->gkey1 : c->gkey, 1);
         if (graph_ok && !step_rc) {
@@ -699,9 +698,9 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
             for (int i = 0; i < nrem; ++i) HIPCHK(c, hipGraphLaunch(gsteps > 1 ? c->gexec1 : c->gexec, st));
             c->stats.graph_used = 1;
         } else if (!step_rc) {
-            early(true); for (int i = 0; i < n_early; ++i) enqueue_steps(1); early(false);
+            for (int i = 0; i < n_early; ++i) enqueue_steps(1, true);
             if (n_early > 0 && nmain > 0) car_launch_set_pos_step(pos, c->h_init2[0], c->h_init2[1], st);
-            for (int i = 0; i < nmain; ++i) enqueue_steps(1);
+            for (int i = 0; i < nmain; ++i) enqueue_steps(1, false);
         }
     }
     if (step_rc) { fence_out(c, caller); return -1; }        // c->err was set by the step builder

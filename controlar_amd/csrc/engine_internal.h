@@ -22,6 +22,7 @@
 #include "kernel_params.h"
 extern "C" {
 int car_launch_dec_gemm_cfg(const GemmDP* p, int epi, int cfg, hipStream_t st);
+int car_launch_dec_gemm_cfg_ex(const GemmDP* p, int epi, int cfg, int staged_ok, hipStream_t st);
 int car_pick_gemm_cfg(int M, int N, int K, int epi);
 void car_launch_dec_attn2_var(const Attn2P* p, int b, int variant, int lds_pad, hipStream_t st);
 void car_launch_mask_first_valid(const unsigned char* mask, int* jmin, int b, int T, hipStream_t st);

@@ -651,6 +651,35 @@ def test_small_chain_runahead_and_attention_do_not_change_a_bit(B, cfg_scale, mo
     eng.close()
 
 
+def test_switch_changed_between_calls_is_recaptured_not_replayed(monkeypatch):
+    """The graph-cache key is the decode plan: a schedule switch flipped between two calls on ONE engine must give a new capture.  The schedule-invariance tests
+    above cannot see a stale replay (every schedule computes the same bits); the kernel count of the captured step can: CAR_ATTN_SPLIT_SMALL turns the one-launch
+    attention of an 8-row chain into split-KV (nsplit = 16) + combine, one more kernel per layer."""
+    from controlar_amd import config as C, synth
+    from controlar_amd.engine import Engine
+    cfg = C.tiny_t2i(64, "canny")
+    gsd, _ = synth.path_state_dicts(cfg, seed=0)
+    B, H, W, n_new = 8, 128, 128, 8
+    img = synth.canny_like_control(B, H, W)
+    emb, mask = synth.text_embeddings(B, cfg.gpt.cls_token_num, cfg.gpt.caption_dim)
+    eng = Engine(cfg, "bf16", dev=True); eng.load_state_dict(gsd); eng.finalize()
+    eng.encode_control(img.cuda())
+    monkeypatch.delenv("CAR_ATTN_SPLIT_SMALL", raising=False)
+    want = eng.generate(emb.cuda(), n_new, mask.cuda(), cfg_scale=1.0).cpu()
+    st = eng.stats(); k0 = st["decode_kernels_per_step"]
+    assert st["graph_used"]
+    monkeypatch.setenv("CAR_ATTN_SPLIT_SMALL", "1")
+    eng.generate(emb.cuda(), n_new, mask.cuda(), cfg_scale=1.0)
+    st = eng.stats()
+    assert st["graph_used"] and st["decode_kernels_per_step"] == k0 + cfg.gpt.n_layer, (k0, st)
+    monkeypatch.delenv("CAR_ATTN_SPLIT_SMALL")
+    got = eng.generate(emb.cuda(), n_new, mask.cuda(), cfg_scale=1.0).cpu()
+    st = eng.stats()
+    assert st["graph_used"] and st["decode_kernels_per_step"] == k0, (k0, st)
+    assert torch.equal(got, want)
+    eng.close()
+
+
 def test_two_chains_free_running_twins_agree_at_model_b():
     """Two decode chains as parallel graph branches, FREE-RUNNING (what bench.py's twin check asserts at XL): identical inputs in row 0 (chain 0) and row B/2
     (chain 1) must give identical tokens and logits on every call.  Round 6 found the teacher-forced comparison blind to a stale step position: a dec_gemm that
