@@ -1,6 +1,7 @@
 """Condition extractors of the path's front end.  ``CannyDetector`` keeps the call shape of the reference's
 ``condition/canny.py:6-14`` (array or tensor (H, W, 3) in, array (H, W) out) and runs ``car_canny`` on the GPU.  ``LineArt`` keeps the call shape of
-``condition/lineart.py:26-86`` (tensor (B, 3, H, W) in, tensor (B, 1, Ho, Wo) in 0..1 out) and runs ``car_lineart``."""
+``condition/lineart.py:26-86`` (tensor (B, 3, H, W) in, tensor (B, 1, Ho, Wo) in 0..1 out) and runs ``car_lineart``.  ``HEDdetector`` keeps the call shape of
+``condition/hed.py:56-81`` (tensor (B, 3, H, W) in, raw 0..255; tensor (B, H, W) in 0..255 out) and runs ``car_hed``."""
 from __future__ import annotations
 
 import numpy as np
@@ -48,3 +49,30 @@ class LineArt:
 
     def __call__(self, x, cond=None):
         return self.forward(x, cond)
+
+
+class HEDdetector:
+    """Drop-in for the reference's ``HEDdetector()`` as the sampling scripts use it (sample_t2i.py:108-109: construct, .to(device), .eval();
+    :126-128: call on a uint8 (B,3,H,W) tensor).  The reference's constructor fetches ``ControlNetHED.pth``; this one never downloads: pass the
+    local file as ``model_path``, or hand the weights to ``load_state_dict``.  The weights live in a context of their own."""
+
+    def __init__(self, model_path=None, precision="bf16", device=None):
+        self.precision = precision
+        self._eng = Engine(tiny_t2i(), precision, device=device)     # the config only shapes the GPT / VQ side, which this context does not hold
+        if model_path is not None:
+            self.load_state_dict(torch.load(model_path, map_location="cpu"))
+
+    def load_state_dict(self, sd, strict=True):
+        """ControlNetHED_Apache2().state_dict() keys, with or without the detector's ``netNetwork.`` prefix."""
+        self._eng.load_hed(sd, finalize=True)
+        return self
+
+    def to(self, device=None, *args, **kwargs):
+        return self
+
+    def eval(self):
+        return self
+
+    def __call__(self, input_image):
+        """input: tensor (B,C,H,W)   output: tensor (B,H,W)   (condition/hed.py:67-81)"""
+        return self._eng.hed(input_image).to(input_image.device)

@@ -137,6 +137,7 @@ struct car_ctx {
                                  // with a system-scope store, and every entry that takes this context reads it without a host wait (check_sticky)
     DevBuf canny_map;    // car_canny: uint8 [B,H,W] candidate/edge map + the "changed" flag
     DevBuf lineart_ws;   // car_lineart: NHWC activations, raw fp32 conv outputs and InstanceNorm partials of one chunk of images (grows on demand)
+    DevBuf hed_ws;       // car_hed: NHWC activations (two rotating buffers) and the side-output partials of one chunk of images (grows on demand)
     car_t5_config t5 = {}; bool has_t5 = false;
     DevBuf t5_in;        // int32 ids [B*T] | uint8 key mask [B*T] | staging for host-side int64 inputs
     DevBuf t5_bias; int t5_bias_T = 0;   // position bias fp32 [heads][T][T] of the last sequence length

@@ -148,6 +148,18 @@ static std::vector<std::string> lineart_tensor_names() {
     return v;
 }
 
+// the 37 tensors of ControlNetHED_Apache2().state_dict() (condition/hed.py:36-44), under the "hed." prefix of the C ABI
+static const int kHedCin[5] = {3, 64, 128, 256, 512}, kHedCout[5] = {64, 128, 256, 512, 512}, kHedConvs[5] = {2, 2, 3, 3, 3};
+static std::vector<std::string> hed_tensor_names() {
+    std::vector<std::string> v = {"hed.norm"};
+    for (int b = 0; b < 5; ++b) {
+        const std::string p = "hed.block" + std::to_string(b + 1) + ".";
+        for (int i = 0; i < kHedConvs[b]; ++i) for (const char* s : {".weight", ".bias"}) v.push_back(p + "convs." + std::to_string(i) + s);
+        v.push_back(p + "projection.weight"); v.push_back(p + "projection.bias");
+    }
+    return v;
+}
+
 extern "C" int car_load_tensor(car_ctx* c, const char* cname, const void* ptr, const int64_t* shape, int32_t ndim, int32_t dtype) {
     if (!c || !cname || !ptr || (ndim > 0 && !shape)) { if (c) c->err = "car_load_tensor: null argument"; return -1; }
     if (dtype != CAR_DT_F32 && dtype != CAR_DT_BF16) FAIL(c, "car_load_tensor(%s): dtype must be F32 or BF16", cname);
@@ -232,6 +244,34 @@ extern "C" int car_load_tensor(car_ctx* c, const char* cname, const void* ptr, c
         std::vector<float> pk((size_t)Co * Kp, 0.f);
         for (int o = 0; o < Co; ++o) for (int ci = 0; ci < Ci; ++ci) for (int t = 0; t < ks * ks; ++t)
             pk[(size_t)o * Kp + (size_t)t * Ci + ci] = h[((size_t)o * Ci + ci) * ks * ks + t];
+        return upload(c, name, pk, {Co, Kp});
+    }
+    if (starts_with(name, "hed.")) {
+        // HED extractor (condition/hed.py:17-53; car_hed).  3x3 conv weights become implicit-GEMM images [Cout][9*Cin] (k = tap*Cin + ci, K padded to the
+        // 32-wide k step: 27 -> 32 for block1.convs.0) in the context's element type; a 1x1 side projection becomes its [Cout] vector in the element type
+        // (the reference projects the stored activation with a conv in the model dtype); norm and every bias stay fp32.
+        int blk = -1;
+        const std::vector<std::string> names = hed_tensor_names();
+        bool known = false;
+        for (auto& r : names) if (r == name) known = true;
+        if (!known) FAIL(c, "%s: not a tensor of the HED network (ControlNetHED_Apache2)", cname);
+        if (name == "hed.norm") {
+            if (n != 3) FAIL(c, "%s: expected [1,3,1,1]", cname);
+            return upload(c, name, h, {3}, true);
+        }
+        blk = name[9] - '1';                          // "hed.blockN."
+        const int Co = kHedCout[blk];
+        if (ends_with(name, "projection.bias")) { if (n != 1) FAIL(c, "%s: expected [1]", cname); return upload(c, name, h, {1}, true); }
+        if (ends_with(name, "projection.weight")) {
+            if (ndim != 4 || shp[0] != 1 || shp[1] != Co || shp[2] != 1 || shp[3] != 1) FAIL(c, "%s: expected [1,%d,1,1]", cname, Co);
+            return upload(c, name, h, {Co});
+        }
+        if (ends_with(name, ".bias")) { if (ndim != 1 || shp[0] != Co) FAIL(c, "%s: expected [%d]", cname, Co); return upload(c, name, h, shp, true); }
+        const int Ci = name.compare(11, 8, "convs.0.") == 0 ? kHedCin[blk] : Co, K = 9 * Ci, Kp = (int)rup((size_t)K, 32);
+        if (ndim != 4 || shp[0] != Co || shp[1] != Ci || shp[2] != 3 || shp[3] != 3) FAIL(c, "%s: expected [%d,%d,3,3]", cname, Co, Ci);
+        std::vector<float> pk((size_t)Co * Kp, 0.f);
+        for (int o = 0; o < Co; ++o) for (int ci = 0; ci < Ci; ++ci) for (int t = 0; t < 9; ++t)
+            pk[(size_t)o * Kp + (size_t)t * Ci + ci] = h[((size_t)o * Ci + ci) * 9 + t];
         return upload(c, name, pk, {Co, Kp});
     }
     if (starts_with(name, "t5.")) {
@@ -357,7 +397,12 @@ extern "C" int car_finalize_weights(car_ctx* c) {
     bool have_la = false;
     for (auto& r : la_names) if (Wp(c, r)) have_la = true;
     if (have_la) for (auto& r : la_names) if (!Wp(c, r)) { if (nmiss < 6) missing += r + " "; ++nmiss; }
-    const bool vq_only = (Wp(c, "quantize.embedding.weight") || have_t5 || have_la) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
+    // so is the HED extractor
+    const std::vector<std::string> hed_names = hed_tensor_names();
+    bool have_hed = false;
+    for (auto& r : hed_names) if (Wp(c, r)) have_hed = true;
+    if (have_hed) for (auto& r : hed_names) if (!Wp(c, r)) { if (nmiss < 6) missing += r + " "; ++nmiss; }
+    const bool vq_only = (Wp(c, "quantize.embedding.weight") || have_t5 || have_la || have_hed) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
     c->has_gpt = !vq_only;
     if (have_t5) {       // the caption encoder is optional as a group, complete if present
         std::vector<std::string> tr = {"t5.encoder.final_layer_norm.weight"};

@@ -57,3 +57,23 @@ struct LaConvP {
     int tile0, tiles_img;             // first InstanceNorm partial slot of this launch; partial slots per image
     signed char dy[49], dx[49];
 };
+
+// ------------------------------------------------------------------ HED extractor (hed.hip; condition/hed.py:17-81)
+// One 3x3 / stride 1 / zero-padded convolution launch as an implicit GEMM: rows = the H x W grid of ONE image (blockIdx.z), k = tap*Cin + ci,
+// weights [N][Kp].  pool = 1: the stored input map is Hi x Wi and the conv reads it through a 2x2 / stride-2 max-pool (H = Hi/2, W = Wi/2, floor).
+// part != NULL: the block's 1x1 side projection is taken in the epilogue — fp32 partial per 64-channel block at part[img*part_img + nblk*H*W + pixel].
+struct HedConvP {
+    const void* in; const void* w; const float* bias; void* out;
+    const void* proj; float* part;
+    long in_img, out_img, part_img;   // per-image element strides
+    int Hi, Wi, H, W;
+    int Cin, N, K, Kp, pool;
+};
+
+// Fusion of the five side maps (level l is (H >> l) x (W >> l), nblk[l] channel-block partials + bias): bilinear up-sampling, mean, sigmoid, x255.
+struct HedFuseP {
+    const float* part[5]; const float* bias[5];
+    long part_img[5]; int nblk[5];
+    float* out; void* control;        // fp32 [nimg][H*W]; T [nimg][3][H*W]
+    int H, W;
+};

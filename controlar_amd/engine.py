@@ -276,6 +276,24 @@ class Engine:
                                          C.c_void_p(ctrl.data_ptr() if ctrl is not None else 0), C.c_void_p(_stream_ptr())), "car_lineart")
         return (out, ctrl) if want_control else out
 
+    def load_hed(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
+        """ControlNetHED_Apache2().state_dict() names (condition/hed.py:36-44: norm, block1.convs.0.weight ... block5.projection.bias), or a
+        HEDdetector's own with the 'netNetwork.' prefix; the C ABI namespaces them under 'hed.'."""
+        pre = "netNetwork."
+        self.load_state_dict({"hed." + (k[len(pre):] if k.startswith(pre) else k): v for k, v in sd.items()}, finalize=finalize)
+
+    def hed(self, img: torch.Tensor, want_control: bool = False):
+        """HEDdetector.__call__ (condition/hed.py:67-81) on the GPU.  img [B,3,H,W] uint8 or float, raw 0..255 values -> fp32 [B,H,W] in 0..255; with
+        want_control also the control tensor [B,3,H,W] = 2*(out/255 - 0.5) in the context's element type (sample_t2i.py:128,141)."""
+        assert img.dim() == 4 and img.shape[1] == 3, "expected an image batch [B, 3, H, W]"
+        x = img.to(device=self.device, dtype=torch.float32).contiguous()
+        B, _, H, W = x.shape
+        out = torch.empty(B, H, W, dtype=torch.float32, device=self.device)
+        ctrl = torch.empty(B, 3, H, W, dtype=self.dtype, device=self.device) if want_control else None
+        self._check(self.lib.car_hed(self._h, C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()),
+                                     C.c_void_p(ctrl.data_ptr() if ctrl is not None else 0), C.c_void_p(_stream_ptr())), "car_hed")
+        return (out, ctrl) if want_control else out
+
     # ------------------------------------------------------------------ caption encoder (language/t5.py)
     def t5_configure(self, t5cfg):
         tc = L.CarT5Config()

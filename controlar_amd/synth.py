@@ -375,3 +375,24 @@ def lineart_state_dict(seed: int = 11) -> Dict[str, torch.Tensor]:
     convt("model3.3", 128, 64)
     conv("model4.1", 1, 64, 7, gain=3.0)
     return sd
+
+
+HED_BLOCKS = ((3, 64, 2), (64, 128, 2), (128, 256, 3), (256, 512, 3), (512, 512, 3))     # (Cin, Cout, convs) of block1..5 (condition/hed.py:40-44)
+
+
+def hed_state_dict(seed: int = 11, proj_gain: float = 0.05) -> Dict[str, torch.Tensor]:
+    """ControlNetHED_Apache2().state_dict() names and shapes (reference condition/hed.py:17-53): 37 tensors, 14.7 M parameters.  The stock initialisation
+    has norm = 0 and tiny side outputs (a flat 127.5 everywhere); here conv weights are N(0, 2/fan_in) (He: the ReLU chain keeps its scale), biases
+    N(0, 0.1^2), norm close to the channel means of natural images, and the 1x1 side projections N(0, proj_gain^2 / Cout), which spreads the fused
+    sigmoid over most of 0..255 without saturating it."""
+    r = _Rng(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    sd["norm"] = torch.tensor([123.7, 116.3, 103.5]).view(1, 3, 1, 1) + r.normal(1, 3, 1, 1, std=0.5)
+    for b, (ci, co, n) in enumerate(HED_BLOCKS, 1):
+        for i in range(n):
+            cin = ci if i == 0 else co
+            sd[f"block{b}.convs.{i}.weight"] = r.normal(co, cin, 3, 3, std=(2.0 / (cin * 9)) ** 0.5)
+            sd[f"block{b}.convs.{i}.bias"] = r.normal(co, std=0.1)
+        sd[f"block{b}.projection.weight"] = r.normal(1, co, 1, 1, std=proj_gain * co ** -0.5)
+        sd[f"block{b}.projection.bias"] = r.normal(1, std=0.1)
+    return sd

@@ -178,6 +178,20 @@ int car_lineart(car_ctx* ctx, const float* img_nchw, int32_t B, int32_t H, int32
                 float* out, void* control_out, void* stream);
 
 /*
+ * HED edge extraction — replaces HEDdetector.__call__ (condition/hed.py:17-81: ControlNetHED_Apache2, bilinear up-sampling of the five side outputs,
+ * mean, sigmoid, x255; callers sample_t2i.py:108-109,126-128, sample_t2i_MR.py, autoregressive/test/test_t2i.py:172-173, test_c2i.py,
+ * evaluations/hed_ssim.py).  img_nchw: fp32 [B,3,H,W] (device), raw 0..255 values as the reference receives them.  out: fp32 [B,H,W] in 0..255 or NULL;
+ * control_out: [B,3,H,W] in the context's element type, = 2*(out/255 - 0.5) replicated over 3 channels (sample_t2i.py:128,141), ready for
+ * car_encode_control, or NULL; not both NULL.  H or W below 16 is an error (four 2x2 pools leave nothing; the reference raises there).  The context's
+ * mode sets the arithmetic: bf16 operands and activations with fp32 accumulation, or fp32 throughout; side outputs, up-sampling and the sigmoid are
+ * fp32 in both.  Weights: the 37 tensors of ControlNetHED_Apache2().state_dict() through car_load_tensor under "hed." + key (norm,
+ * block1.convs.0.weight ... block5.projection.bias), then car_finalize_weights; a context may hold them alone or next to a GPT / VQ / T5 / LineArt
+ * model.  Deterministic (no atomics), batch-invariant per image, no host synchronisation.
+ */
+int car_hed(car_ctx* ctx, const float* img_nchw, int32_t B, int32_t H, int32_t W,
+            float* out, void* control_out, void* stream);
+
+/*
  * Caption encoder — replaces T5Embedder.get_text_embeddings' model call (language/t5.py:185-201:
  * self.model(input_ids, attention_mask)['last_hidden_state'], HF T5EncoderModel built at language/t5.py:58-79; callers
  * sample_t2i.py:99-118, demo/model.py).  The tokenizer stays on the host side of the boundary (sentencepiece, CPU string work).
