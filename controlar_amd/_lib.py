@@ -43,6 +43,14 @@ class CarT5Config(C.Structure):
     ]
 
 
+class CarDptConfig(C.Structure):
+    _fields_ = [
+        ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("mlp", C.c_int32), ("pos_grid", C.c_int32),
+        ("out_indices", C.c_int32 * 4), ("neck_hidden", C.c_int32 * 4), ("fusion_hidden", C.c_int32), ("ln_eps", C.c_float),
+        ("reserved", C.c_int32 * 8),
+    ]
+
+
 class CarSampling(C.Structure):
     _fields_ = [
         ("cfg_scale", C.c_float), ("cfg_interval", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32),
@@ -81,6 +89,8 @@ SYMBOLS = {
     "car_canny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_lineart": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_hed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_depth_configure": (C.c_int, [C.c_void_p, C.POINTER(CarDptConfig)]),
+    "car_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_vq_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "car_vq_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "car_get_stats": (C.c_int, [C.c_void_p, C.POINTER(CarStats)]),

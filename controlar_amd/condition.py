@@ -76,3 +76,55 @@ class HEDdetector:
     def __call__(self, input_image):
         """input: tensor (B,C,H,W)   output: tensor (B,H,W)   (condition/hed.py:67-81)"""
         return self._eng.hed(input_image).to(input_image.device)
+
+
+class _DepthOutput:
+    def __init__(self, predicted_depth):
+        self.predicted_depth = predicted_depth
+
+
+class DepthEstimator:
+    """Stands where the sampling scripts hold ``DPTForDepthEstimation.from_pretrained("dpt_large")`` and its image processor (sample_t2i.py:33,114-116,
+    133-139): ``from_pretrained(local_dir)``, ``.to(device)``, ``.eval()``, ``model(pixel_values=...).predicted_depth``.  ``from_pretrained`` reads
+    ``config.json`` and ``model.safetensors`` (or ``pytorch_model.bin``) from a LOCAL directory and never downloads.  ``preprocess`` is the processor's
+    rescale and normalise ((x/255 - 0.5)/0.5); the processor's PIL resize to the model's square input size stays with the caller: this class takes
+    square images whose side is a multiple of 32.  The weights live in a context of their own."""
+
+    def __init__(self, cfg, state_dict=None, precision="bf16", device=None):
+        self.config = cfg
+        self.precision = precision
+        self._eng = Engine(tiny_t2i(), precision, device=device)     # the config only shapes the GPT / VQ side, which this context does not hold
+        if state_dict is not None:
+            self._eng.load_depth(state_dict, cfg, finalize=True)
+
+    @classmethod
+    def from_pretrained(cls, local_dir, precision="bf16", device=None):
+        import json
+        import os
+        from .checkpoint import load_checkpoint, _torch_load
+        from .config import DPTConfig
+        with open(os.path.join(local_dir, "config.json")) as f:
+            cfg = DPTConfig.from_hf_dict(json.load(f))
+        st = os.path.join(local_dir, "model.safetensors")
+        if os.path.exists(st):
+            sd = load_checkpoint(st)
+        else:
+            sd = _torch_load(os.path.join(local_dir, "pytorch_model.bin"))
+            for k in ("state_dict", "model"):
+                if k in sd and isinstance(sd[k], dict):
+                    sd = sd[k]
+        return cls(cfg, sd, precision=precision, device=device)
+
+    @staticmethod
+    def preprocess(images):
+        """uint8 [B,3,S,S] -> fp32 pixel_values: rescale by 1/255, normalise with mean = std = 0.5 (DPTImageProcessor's defaults for dpt-large)."""
+        return (images.to(torch.float32) / 255 - 0.5) / 0.5
+
+    def to(self, device=None, *args, **kwargs):
+        return self
+
+    def eval(self):
+        return self
+
+    def __call__(self, pixel_values=None, **kwargs):
+        return _DepthOutput(self._eng.depth(pixel_values).to(pixel_values.device))

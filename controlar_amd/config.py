@@ -7,8 +7,9 @@ instantiated by autoregressive/models/dinov2_adapter.py:13).  Nothing here compu
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass, field, asdict
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 
 def find_multiple(n: int, k: int) -> int:
@@ -118,6 +119,90 @@ def tiny_t5() -> T5Config:
 def small_t5() -> T5Config:
     """t5-small-shaped gated variant (8 heads x 64): mid-size parity case."""
     return T5Config(vocab_size=4096, d_model=512, d_kv=64, num_heads=8, d_ff=1024, num_layers=4)
+
+
+@dataclass
+class DPTConfig:
+    """HF DPTConfig fields that DPTForDepthEstimation reads (sample_t2i.py:33,114-116 loads Intel/dpt-large).  The library runs the shipped family only:
+    the fields below the blank line are fixed, and ``Engine.load_depth`` refuses any other value at configure time."""
+    hidden_size: int = 1024
+    num_hidden_layers: int = 24
+    num_attention_heads: int = 16
+    intermediate_size: int = 4096
+    image_size: int = 384                  # the checkpoint's position grid is image_size / patch_size
+    patch_size: int = 16
+    backbone_out_indices: Tuple[int, ...] = (5, 11, 17, 23)
+    neck_hidden_sizes: Tuple[int, ...] = (256, 512, 1024, 1024)
+    fusion_hidden_size: int = 256
+    layer_norm_eps: float = 1e-12
+
+    readout_type: str = "project"
+    reassemble_factors: Tuple[float, ...] = (4, 2, 1, 0.5)
+    hidden_act: str = "gelu"
+    qkv_bias: bool = True
+    is_hybrid: bool = False
+    use_batch_norm_in_fusion_residual: bool = False
+    use_bias_in_fusion_residual: Optional[bool] = None      # None = "not use_batch_norm" = True
+    add_projection: bool = False
+    head_in_index: int = -1
+    neck_ignore_stages: Tuple[int, ...] = ()
+    backbone_config: Optional[dict] = None
+
+    @property
+    def pos_grid(self) -> int:
+        return self.image_size // self.patch_size
+
+    def family_errors(self):
+        """Why this config lies outside what car_depth runs (empty list: inside)."""
+        bad = []
+        if self.is_hybrid or self.backbone_config is not None:
+            bad.append("hybrid / external backbones are not supported (plain ViT only)")
+        if self.readout_type != "project":
+            bad.append(f"readout_type {self.readout_type!r} (only 'project')")
+        if self.use_batch_norm_in_fusion_residual:
+            bad.append("batch norm in the fusion residual units")
+        if self.use_bias_in_fusion_residual is False:
+            bad.append("fusion residual convolutions without bias")
+        if self.add_projection:
+            bad.append("add_projection")
+        if self.patch_size != 16 or self.image_size % self.patch_size:
+            bad.append("patch_size must be 16 and divide image_size")
+        if self.hidden_act != "gelu" or not self.qkv_bias:
+            bad.append("hidden_act must be 'gelu' (erf) with qkv_bias")
+        if tuple(float(f) for f in self.reassemble_factors) != (4.0, 2.0, 1.0, 0.5):
+            bad.append("reassemble_factors must be (4, 2, 1, 0.5)")
+        if len(self.backbone_out_indices) != 4 or len(self.neck_hidden_sizes) != 4:
+            bad.append("four backbone_out_indices and four neck_hidden_sizes")
+        if self.head_in_index != -1 or tuple(self.neck_ignore_stages):
+            bad.append("head_in_index must be -1 and neck_ignore_stages empty")
+        return bad
+
+    @classmethod
+    def from_hf_dict(cls, d: dict) -> "DPTConfig":
+        """From the ``config.json`` next to an HF checkpoint; keys this class does not know are ignored."""
+        known = {f for f in cls.__dataclass_fields__}
+        kw = {k: (tuple(v) if isinstance(v, list) else v) for k, v in d.items() if k in known}
+        return cls(**kw)
+
+    def to_hf_dict(self) -> dict:
+        return {k: (list(v) if isinstance(v, tuple) else v) for k, v in dataclasses.asdict(self).items()}
+
+
+def dpt_large() -> DPTConfig:
+    """Intel/dpt-large: ViT-L/16, 24 layers, taps after layers 5 / 11 / 17 / 23."""
+    return DPTConfig()
+
+
+def tiny_dpt() -> DPTConfig:
+    """Smallest member of the family that still takes every path: two 64-wide heads (the fused attention kernel in bf16), a 4x4 position grid."""
+    return DPTConfig(hidden_size=128, num_hidden_layers=4, num_attention_heads=2, intermediate_size=512, image_size=64,
+                     backbone_out_indices=(0, 1, 2, 3), neck_hidden_sizes=(64, 64, 128, 128), fusion_hidden_size=64)
+
+
+def tiny_dpt_wide() -> DPTConfig:
+    """The DPT-base neck widths (96 and 192 are no multiples of the conv kernel's 64-channel tile) on a small backbone."""
+    return DPTConfig(hidden_size=256, num_hidden_layers=4, num_attention_heads=4, intermediate_size=1024, image_size=64,
+                     backbone_out_indices=(0, 1, 2, 3), neck_hidden_sizes=(96, 192, 384, 384), fusion_hidden_size=128)
 
 
 @dataclass

@@ -138,6 +138,9 @@ struct car_ctx {
     DevBuf canny_map;    // car_canny: uint8 [B,H,W] candidate/edge map + the "changed" flag
     DevBuf lineart_ws;   // car_lineart: NHWC activations, raw fp32 conv outputs and InstanceNorm partials of one chunk of images (grows on demand)
     DevBuf hed_ws;       // car_hed: NHWC activations (two rotating buffers) and the side-output partials of one chunk of images (grows on demand)
+    car_dpt_config dpt = {}; bool has_dpt = false;   // car_depth_configure
+    std::map<int, void*> depth_pos_cache;   // token grid -> T [1 + g*g, hidden]: depth.dpt.embeddings.position_embeddings resized bilinearly
+    DevBuf depth_ws;     // car_depth: the neck's feature maps, three rotating activation buffers, the fp32 map and the per-image maxima of one chunk of images
     car_t5_config t5 = {}; bool has_t5 = false;
     DevBuf t5_in;        // int32 ids [B*T] | uint8 key mask [B*T] | staging for host-side int64 inputs
     DevBuf t5_bias; int t5_bias_T = 0;   // position bias fp32 [heads][T][T] of the last sequence length
@@ -243,6 +246,9 @@ static inline void mlp_tanh(car_ctx* c, const void* x, long lda, long sA, int nb
 
 static inline void fence_in(car_ctx* c, hipStream_t caller) { (void)hipEventRecord(c->ev_in, caller); (void)hipStreamWaitEvent(c->stream, c->ev_in, 0); }
 static inline void fence_out(car_ctx* c, hipStream_t caller) { (void)hipEventRecord(c->ev_out, c->stream); (void)hipStreamWaitEvent(caller, c->ev_out, 0); }
+
+// engine_depth.hip: every tensor a configured DPT needs, under its "depth." name (car_finalize_weights, car_load_tensor)
+std::vector<std::string> depth_tensor_names(const car_dpt_config& d);
 
 // engine_encode.hip
 int get_resize(car_ctx* c, int H, int W, int nh, int nw, car_ctx::ResizeTab* out);

@@ -274,6 +274,81 @@ extern "C" int car_load_tensor(car_ctx* c, const char* cname, const void* ptr, c
             pk[(size_t)o * Kp + (size_t)t * Ci + ci] = h[((size_t)o * Ci + ci) * 9 + t];
         return upload(c, name, pk, {Co, Kp});
     }
+    if (starts_with(name, "depth.")) {
+        // DPT depth estimator (modeling_dpt.py DPTForDepthEstimation; car_depth).  Linear weights, LayerNorm parameters and every bias a car_launch_gemm
+        // epilogue adds stay [N, K] / [N] in the context's element type; 1x1 convs drop their trailing 1x1; 3x3 conv weights become implicit-GEMM images
+        // [Cout][9*Cin] (k = tap*Cin + ci); a ConvTranspose2d(k = stride) weight [Cin, Cout, k, k] becomes the GEMM image [(ky*k + kx)*Cout + co][ci] and its
+        // bias is replicated per tap; the biases dpt_conv adds in its fp32 epilogue stay fp32; position_embeddings stays on the host (resized per grid).
+        if (!c->has_dpt) FAIL(c, "%s: call car_depth_configure before loading depth.* tensors", cname);
+        if (starts_with(name, "depth.dpt.layernorm.") || starts_with(name, "depth.dpt.pooler.")) return 0;     // never reach the depth map
+        const car_dpt_config& d = c->dpt;
+        bool known = false;
+        for (auto& r : depth_tensor_names(d)) if (r == name) { known = true; break; }
+        if (!known) FAIL(c, "%s: not a tensor of the configured DPT depth estimator (DPTForDepthEstimation)", cname);
+        const std::string key = name.substr(6);
+        const int64_t D = d.hidden, Fh = d.fusion_hidden, G = d.pos_grid;
+        auto is_shape = [&](std::initializer_list<int64_t> ex) { return shp.size() == ex.size() && std::equal(ex.begin(), ex.end(), shp.begin()); };
+        auto conv3 = [&](int64_t Co, int64_t Ci) -> int {
+            if (!is_shape({Co, Ci, 3, 3})) FAIL(c, "%s: expected [%lld,%lld,3,3]", cname, (long long)Co, (long long)Ci);
+            std::vector<float> pk((size_t)Co * 9 * Ci);
+            for (int64_t o = 0; o < Co; ++o) for (int64_t ci = 0; ci < Ci; ++ci) for (int t = 0; t < 9; ++t)
+                pk[((size_t)o * 9 + t) * Ci + ci] = h[((size_t)o * Ci + ci) * 9 + t];
+            return upload(c, name, pk, {Co, 9 * Ci});
+        };
+        auto vec = [&](int64_t N, bool f32) -> int { if (!is_shape({N})) FAIL(c, "%s: expected [%lld]", cname, (long long)N); return upload(c, name, h, shp, f32); };
+        auto mat = [&](int64_t N, int64_t K) -> int {          // Linear [N,K] or 1x1 conv [N,K,1,1]
+            if (!is_shape({N, K}) && !is_shape({N, K, 1, 1})) FAIL(c, "%s: expected [%lld,%lld]", cname, (long long)N, (long long)K);
+            return upload(c, name, h, {N, K});
+        };
+        const bool isw = ends_with(name, ".weight");
+        int i = -1;
+        if (key == "dpt.embeddings.cls_token") { if (n != D) FAIL(c, "%s: expected [1,1,%lld]", cname, (long long)D); return upload(c, name, h, {D}); }
+        if (key == "dpt.embeddings.position_embeddings") {
+            if (n != (G * G + 1) * D) FAIL(c, "%s: expected [1,%lld,%lld]", cname, (long long)(G * G + 1), (long long)D);
+            for (auto& kv : c->depth_pos_cache) (void)hipFree(kv.second);
+            c->depth_pos_cache.clear(); c->host_keep[name] = h; return 0;
+        }
+        if (key == "dpt.embeddings.patch_embeddings.projection.weight") { if (!is_shape({D, 3, 16, 16})) FAIL(c, "%s: expected [%lld,3,16,16]", cname, (long long)D); return upload(c, name, h, {D, 768}); }
+        if (key == "dpt.embeddings.patch_embeddings.projection.bias") return vec(D, false);
+        if (starts_with(key, "dpt.encoder.layer.")) {
+            if (ends_with(key, "intermediate.dense.weight")) return mat(d.mlp, D);
+            if (ends_with(key, "intermediate.dense.bias")) return vec(d.mlp, false);
+            if (ends_with(key, "attention.output.dense.weight")) return mat(D, D);
+            if (ends_with(key, "output.dense.weight")) return mat(D, d.mlp);
+            if (isw && key.find("layernorm_") == std::string::npos) return mat(D, D);
+            return vec(D, false);
+        }
+        if (sscanf(key.c_str(), "neck.reassemble_stage.readout_projects.%d.", &i) == 1) return isw ? mat(D, 2 * D) : vec(D, false);
+        if (sscanf(key.c_str(), "neck.reassemble_stage.layers.%d.", &i) == 1) {
+            const int64_t Ci = d.neck_hidden[i];
+            if (key.find(".projection.") != std::string::npos) return isw ? mat(Ci, D) : vec(Ci, false);
+            if (i == 3) return isw ? conv3(Ci, Ci) : vec(Ci, true);
+            const int k = i == 0 ? 4 : 2;
+            if (!isw) {
+                if (!is_shape({Ci})) FAIL(c, "%s: expected [%lld]", cname, (long long)Ci);
+                std::vector<float> rep((size_t)k * k * Ci);
+                for (int t = 0; t < k * k; ++t) memcpy(&rep[(size_t)t * Ci], h.data(), (size_t)Ci * 4);
+                return upload(c, name, rep, {(int64_t)k * k * Ci});
+            }
+            if (!is_shape({Ci, Ci, k, k})) FAIL(c, "%s: expected [%lld,%lld,%d,%d]", cname, (long long)Ci, (long long)Ci, k, k);
+            std::vector<float> pk((size_t)k * k * Ci * Ci);
+            for (int64_t ci = 0; ci < Ci; ++ci) for (int64_t co = 0; co < Ci; ++co) for (int t = 0; t < k * k; ++t)
+                pk[((size_t)t * Ci + co) * Ci + ci] = h[((size_t)ci * Ci + co) * k * k + t];
+            return upload(c, name, pk, {(int64_t)k * k * Ci, Ci});
+        }
+        if (sscanf(key.c_str(), "neck.convs.%d.", &i) == 1) return conv3(Fh, d.neck_hidden[i]);
+        if (starts_with(key, "neck.fusion_stage.layers.")) {
+            if (key.find(".projection.") != std::string::npos) return isw ? mat(Fh, Fh) : vec(Fh, false);
+            return isw ? conv3(Fh, Fh) : vec(Fh, true);
+        }
+        if (key == "head.head.0.weight") return conv3(Fh / 2, Fh);
+        if (key == "head.head.0.bias") return vec(Fh / 2, true);
+        if (key == "head.head.2.weight") return conv3(32, Fh / 2);
+        if (key == "head.head.2.bias") return vec(32, true);
+        if (key == "head.head.4.weight") { if (!is_shape({1, 32, 1, 1})) FAIL(c, "%s: expected [1,32,1,1]", cname); return upload(c, name, h, {32}); }
+        if (key == "head.head.4.bias") return vec(1, true);
+        FAIL(c, "%s: not a tensor of the configured DPT depth estimator", cname);
+    }
     if (starts_with(name, "t5.")) {
         // caption encoder (car_t5_encode).  A full T5 state dict may be offered: the decoder half, lm_head and the tied alias are skipped.
         if (!c->has_t5) FAIL(c, "%s: call car_t5_configure before loading t5.* tensors", cname);
@@ -402,7 +477,15 @@ extern "C" int car_finalize_weights(car_ctx* c) {
     bool have_hed = false;
     for (auto& r : hed_names) if (Wp(c, r)) have_hed = true;
     if (have_hed) for (auto& r : hed_names) if (!Wp(c, r)) { if (nmiss < 6) missing += r + " "; ++nmiss; }
-    const bool vq_only = (Wp(c, "quantize.embedding.weight") || have_t5 || have_la || have_hed) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
+    // and the DPT depth estimator (position_embeddings lives on the host)
+    bool have_dpt = false;
+    if (c->has_dpt) {
+        const std::vector<std::string> dn = depth_tensor_names(c->dpt);
+        auto have = [&](const std::string& r) { return Wp(c, r) || c->host_keep.find(r) != c->host_keep.end(); };
+        for (auto& r : dn) if (have(r)) have_dpt = true;
+        if (have_dpt) for (auto& r : dn) if (!have(r)) { if (nmiss < 6) missing += r + " "; ++nmiss; }
+    }
+    const bool vq_only = (Wp(c, "quantize.embedding.weight") || have_t5 || have_la || have_hed || have_dpt) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
     c->has_gpt = !vq_only;
     if (have_t5) {       // the caption encoder is optional as a group, complete if present
         std::vector<std::string> tr = {"t5.encoder.final_layer_norm.weight"};

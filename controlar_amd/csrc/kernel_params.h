@@ -77,3 +77,18 @@ struct HedFuseP {
     float* out; void* control;        // fp32 [nimg][H*W]; T [nimg][3][H*W]
     int H, W;
 };
+
+// ------------------------------------------------------------------ DPT depth estimator (dpt.hip; transformers modeling_dpt.py neck + head)
+// One 3x3 / zero-padded (pad 1) convolution launch as an implicit GEMM: rows = the H x W output grid of ONE image (blockIdx.z), k = tap*Cin + ci
+// (Cin a multiple of 32), weights [N][9*Cin], N a multiple of 4 (partial 64-channel tiles are masked).  stride 1: H = Hi, W = Wi; stride 2:
+// H = (Hi-1)/2 + 1, likewise W.  relu_in: the gather reads max(x, 0) (the pre-activation of a residual conv unit).  Epilogue, in this order:
+// + bias (optional), + res1, + res2 (optional NHWC maps of the output's shape), ReLU (relu_out), round to T, store (out may be NULL with proj).
+// proj != NULL (N <= 64): the T-rounded channels are reduced against proj[N] in fp32, + proj_bias[0], ReLU -> map[img*map_img + pixel] (fp32).
+struct DptConvP {
+    const void* in; const void* w; const float* bias; void* out;
+    const void* res1; const void* res2;
+    const void* proj; const float* proj_bias; float* map;
+    long in_img, out_img, res1_img, res2_img, map_img;   // per-image element strides
+    int Hi, Wi, H, W;
+    int Cin, N, K, stride, relu_in, relu_out;
+};

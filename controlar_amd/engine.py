@@ -294,6 +294,38 @@ class Engine:
                                      C.c_void_p(ctrl.data_ptr() if ctrl is not None else 0), C.c_void_p(_stream_ptr())), "car_hed")
         return (out, ctrl) if want_control else out
 
+    def depth_configure(self, dcfg):
+        """car_depth_configure from a config.DPTConfig.  A config outside the shipped family (hybrid, readout other than 'project', batch norm in the
+        fusion residual units, ...) is refused here, before any tensor is loaded."""
+        bad = dcfg.family_errors()
+        if bad:
+            raise ValueError("DPT config outside the supported family: " + "; ".join(bad))
+        dc = L.CarDptConfig()
+        dc.hidden, dc.layers, dc.heads, dc.mlp = dcfg.hidden_size, dcfg.num_hidden_layers, dcfg.num_attention_heads, dcfg.intermediate_size
+        dc.pos_grid, dc.fusion_hidden, dc.ln_eps = dcfg.pos_grid, dcfg.fusion_hidden_size, dcfg.layer_norm_eps
+        for i in range(4):
+            dc.out_indices[i], dc.neck_hidden[i] = dcfg.backbone_out_indices[i], dcfg.neck_hidden_sizes[i]
+        self._check(self.lib.car_depth_configure(self._h, C.byref(dc)), "car_depth_configure")
+        self.dptcfg = dcfg
+
+    def load_depth(self, sd: Dict[str, torch.Tensor], cfg, finalize: bool = True):
+        """DPTForDepthEstimation.state_dict() names (dpt.embeddings.cls_token ... head.head.4.bias); the C ABI namespaces them under 'depth.'."""
+        self.depth_configure(cfg)
+        self.load_state_dict({"depth." + k: v for k, v in sd.items()}, finalize=finalize)
+
+    def depth(self, pixel_values: torch.Tensor, want_control: bool = False):
+        """DPTForDepthEstimation(pixel_values).predicted_depth on the GPU.  pixel_values [B,3,S,S] float, what the HF image processor hands the model
+        (rescaled and normalised); S a multiple of 32 -> fp32 [B,S,S] >= 0; with want_control also the control tensor [B,3,S,S] = 2*(d/max - 0.5), the
+        maximum taken per image, in the context's element type (sample_t2i.py:133-141)."""
+        assert pixel_values.dim() == 4 and pixel_values.shape[1] == 3, "expected pixel_values [B, 3, H, W]"
+        x = pixel_values.to(device=self.device, dtype=torch.float32).contiguous()
+        B, _, H, W = x.shape
+        out = torch.empty(B, H, W, dtype=torch.float32, device=self.device)
+        ctrl = torch.empty(B, 3, H, W, dtype=self.dtype, device=self.device) if want_control else None
+        self._check(self.lib.car_depth(self._h, C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(ctrl.data_ptr() if ctrl is not None else 0), C.c_void_p(_stream_ptr())), "car_depth")
+        return (out, ctrl) if want_control else out
+
     # ------------------------------------------------------------------ caption encoder (language/t5.py)
     def t5_configure(self, t5cfg):
         tc = L.CarT5Config()

@@ -15,7 +15,7 @@ from typing import Dict
 
 import torch
 
-from .config import PathConfig, GPTConfig, ViTConfig, VQConfig, T5Config
+from .config import PathConfig, GPTConfig, ViTConfig, VQConfig, T5Config, DPTConfig
 
 
 class _Rng:
@@ -395,4 +395,65 @@ def hed_state_dict(seed: int = 11, proj_gain: float = 0.05) -> Dict[str, torch.T
             sd[f"block{b}.convs.{i}.bias"] = r.normal(co, std=0.1)
         sd[f"block{b}.projection.weight"] = r.normal(1, co, 1, 1, std=proj_gain * co ** -0.5)
         sd[f"block{b}.projection.bias"] = r.normal(1, std=0.1)
+    return sd
+
+
+def dpt_state_dict(cfg: DPTConfig, seed: int = 13) -> Dict[str, torch.Tensor]:
+    """DPTForDepthEstimation(cfg).state_dict() names and shapes (transformers modeling_dpt.py, non-hybrid, readout 'project').  The stock initialisation
+    (std 0.02, zero biases, zero position embeddings) gives a nearly constant map; here weights are N(0, 1/fan_in) (a ConvTranspose2d whose kernel equals
+    its stride sees Cin inputs per output), biases 0.1 N(0,1), LayerNorm weights 1 + 0.1 N(0,1), cls and position embeddings 0.5 N(0,1), and the last
+    bias is 1 so that the final ReLU clips only part of the map."""
+    r = _Rng(seed)
+    D, I, F = cfg.hidden_size, cfg.intermediate_size, cfg.fusion_hidden_size
+    sd: Dict[str, torch.Tensor] = {}
+
+    def lin(name, co, ci):
+        sd[name + ".weight"] = r.normal(co, ci, std=ci ** -0.5)
+        sd[name + ".bias"] = r.normal(co, std=0.1)
+
+    def conv(name, co, ci, k, bias=True):
+        sd[name + ".weight"] = r.normal(co, ci, k, k, std=(ci * k * k) ** -0.5)
+        if bias:
+            sd[name + ".bias"] = r.normal(co, std=0.1)
+
+    def ln(name):
+        sd[name + ".weight"] = 1.0 + r.normal(D, std=0.1)
+        sd[name + ".bias"] = r.normal(D, std=0.1)
+
+    sd["dpt.embeddings.cls_token"] = r.normal(1, 1, D, std=0.5)
+    sd["dpt.embeddings.position_embeddings"] = r.normal(1, cfg.pos_grid ** 2 + 1, D, std=0.5)
+    conv("dpt.embeddings.patch_embeddings.projection", D, 3, cfg.patch_size)
+    for l in range(cfg.num_hidden_layers):
+        p = f"dpt.encoder.layer.{l}."
+        for m in ("query", "key", "value"):
+            lin(p + "attention.attention." + m, D, D)
+        lin(p + "attention.output.dense", D, D)
+        lin(p + "intermediate.dense", I, D)
+        lin(p + "output.dense", D, I)
+        ln(p + "layernorm_before")
+        ln(p + "layernorm_after")
+    ln("dpt.layernorm")                                     # part of the state dict; never reaches the depth map
+    for i, (c, f) in enumerate(zip(cfg.neck_hidden_sizes, cfg.reassemble_factors)):
+        p = f"neck.reassemble_stage.layers.{i}."
+        conv(p + "projection", c, D, 1)
+        if f > 1:
+            k = int(f)
+            sd[p + "resize.weight"] = r.normal(c, c, k, k, std=c ** -0.5)       # [Cin, Cout, k, k]
+            sd[p + "resize.bias"] = r.normal(c, std=0.1)
+        elif f < 1:
+            conv(p + "resize", c, c, 3)
+    for i in range(4):
+        lin(f"neck.reassemble_stage.readout_projects.{i}.0", D, 2 * D)
+    for i, c in enumerate(cfg.neck_hidden_sizes):
+        conv(f"neck.convs.{i}", F, c, 3, bias=False)
+    for i in range(4):
+        p = f"neck.fusion_stage.layers.{i}."
+        conv(p + "projection", F, F, 1)
+        for u in ("residual_layer1", "residual_layer2"):
+            conv(p + u + ".convolution1", F, F, 3)
+            conv(p + u + ".convolution2", F, F, 3)
+    conv("head.head.0", F // 2, F, 3)
+    conv("head.head.2", 32, F // 2, 3)
+    conv("head.head.4", 1, 32, 1)
+    sd["head.head.4.bias"] = torch.ones(1)
     return sd

@@ -192,6 +192,48 @@ int car_hed(car_ctx* ctx, const float* img_nchw, int32_t B, int32_t H, int32_t W
             float* out, void* control_out, void* stream);
 
 /*
+ * DPT depth estimation — replaces DPTForDepthEstimation(pixel_values).predicted_depth and the scaling behind it (sample_t2i.py:33,114-116,133-139;
+ * demo/model.py:192-284): a plain ViT backbone, the readout-"project" reassemble stage, the four-level fusion stage and the three-conv head of
+ * transformers' modeling_dpt.py.  Configure once, load every tensor of DPTForDepthEstimation.state_dict() through car_load_tensor under
+ * "depth." + key (depth.dpt.embeddings.cls_token, depth.dpt.encoder.layer.N.attention.attention.query.weight, depth.neck.reassemble_stage.*,
+ * depth.neck.convs.N.weight, depth.neck.fusion_stage.layers.N.*, depth.head.head.{0,2,4}.*), then car_finalize_weights (which names the first
+ * missing tensor).  depth.dpt.layernorm.* and depth.dpt.pooler.* never reach the depth map: they are accepted and ignored.  Any other "depth.*"
+ * name is refused.  A context may hold these tensors alone or next to any other model; they travel in the packed cache (the importing context is
+ * configured with the same car_dpt_config first).
+ *
+ * The family is the shipped one and nothing else: non-hybrid ViT with patch 16, qkv bias, erf-GELU, readout_type "project", reassemble factors
+ * (4, 2, 1, 1/2), no batch norm in the fusion residual units, no add_projection, head_in_index -1.  car_depth_configure refuses what lies outside
+ * it (sizes that are not multiples of 32, fewer or more than four taps, taps out of order or out of range, and in bf16 mode a head width other
+ * than 64, which the fused attention kernel requires).
+ */
+typedef struct car_dpt_config {
+    int32_t hidden;           /* 1024 (dpt_large) */
+    int32_t layers;           /* 24 */
+    int32_t heads;            /* 16 */
+    int32_t mlp;              /* intermediate_size, 4096 */
+    int32_t pos_grid;         /* image_size / 16 of the checkpoint: 24 */
+    int32_t out_indices[4];   /* backbone_out_indices: 5, 11, 17, 23 */
+    int32_t neck_hidden[4];   /* neck_hidden_sizes: 256, 512, 1024, 1024 */
+    int32_t fusion_hidden;    /* 256 */
+    float   ln_eps;           /* layer_norm_eps, 1e-12 */
+    int32_t reserved[8];      /* zero */
+} car_dpt_config;
+int car_depth_configure(car_ctx* ctx, const car_dpt_config* cfg);
+/*
+ * pixel_values: fp32 [B,3,H,W] (device), exactly what the HF model receives after the image processor's rescale and normalise.  H == W, a
+ * multiple of 32, at least 32: the reference itself raises on a non-square image (its reassemble stage takes sqrt of the token count), and an odd
+ * token grid is out of scope; everything else is an error.  out: fp32 [B,H,W] = predicted_depth (>= 0) or NULL.  control_out: [B,3,H,W] in the
+ * context's element type, = 2*(d/max_b - 0.5) replicated over 3 channels, ready for car_encode_control, or NULL; not both NULL.  max_b is the
+ * maximum of image b alone: the reference takes .max() over a tensor that holds one image, and per image keeps the batch-invariance promise.  The
+ * value is computed in fp32 (correctly rounded division) and rounded once to the element type.  An image whose map is zero everywhere writes -1
+ * (the reference would write NaN).  The position embeddings are resized bilinearly (align_corners = False) in fp32 to the token grid of the call,
+ * once per grid.  The context's mode sets the arithmetic: bf16 operands and activations with fp32 accumulation, or fp32 throughout; the final map
+ * is fp32 in both.  Deterministic (no atomics), batch-invariant per image, no host synchronisation.
+ */
+int car_depth(car_ctx* ctx, const float* pixel_values, int32_t B, int32_t H, int32_t W,
+              float* out, void* control_out, void* stream);
+
+/*
  * Caption encoder — replaces T5Embedder.get_text_embeddings' model call (language/t5.py:185-201:
  * self.model(input_ids, attention_mask)['last_hidden_state'], HF T5EncoderModel built at language/t5.py:58-79; callers
  * sample_t2i.py:99-118, demo/model.py).  The tokenizer stays on the host side of the boundary (sentencepiece, CPU string work).
