@@ -19,6 +19,8 @@ CAR_ABI_VERSION = 2
 CAR_F32, CAR_BF16 = 0, 1
 CAR_DT_F32, CAR_DT_BF16, CAR_DT_I32, CAR_DT_I64, CAR_DT_U8 = 0, 1, 2, 3, 4
 CAR_RESIZE_NEAREST, CAR_RESIZE_BICUBIC_AC = 0, 1
+# car_resize filters: Pillow's own codes (Image.Resampling)
+CAR_FILTER_LANCZOS, CAR_FILTER_BILINEAR, CAR_FILTER_BICUBIC, CAR_FILTER_BOX, CAR_FILTER_HAMMING = 1, 2, 3, 4, 5
 
 
 class CarConfig(C.Structure):
@@ -87,6 +89,8 @@ SYMBOLS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_sample_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CarSampling), C.c_int32, C.c_void_p, C.c_void_p]),
     "car_canny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "car_lineart": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_hed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_depth_configure": (C.c_int, [C.c_void_p, C.POINTER(CarDptConfig)]),
@@ -95,6 +99,7 @@ SYMBOLS = {
     "car_vq_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "car_get_stats": (C.c_int, [C.c_void_p, C.POINTER(CarStats)]),
     "car_debug_pack_decode_weight": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "car_debug_resample_coeffs": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int64]),
     "car_debug_f32_to_e4m3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "car_debug_control_tokens": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
 }

@@ -78,6 +78,8 @@ int car_pick_gemm_f32_cfg(int M, int N, int K, int epi);
 int car_pick_gemm_f32_cfg2(int M, int N, int K, int epi, int chains);
 void car_launch_dec_attn_f32(const AttnFP* p, int b, hipStream_t st);
 void car_launch_dec_attn_f32_ex(const AttnFP* p, int b, int fused, hipStream_t st);
+// resample.hip
+void car_launch_resample(int mode, int pass, const ResampleP* p, hipStream_t st);
 }
 
 
@@ -95,6 +97,14 @@ struct DevBuf {
         cap = want; return true;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// car_resize: the coefficient table of one axis (resample_tab.h), on the host and on the device, with the key it was built for
+struct ResampleAxis {
+    int in_size = 0, out_size = 0, filter = -1; double in0 = 0, in1 = 0;      // the key; filter = -1: empty
+    int ksize = 0, lo = 0, hi = 0;                                            // source indices [lo, hi) are the ones any output index reads
+    std::vector<int32_t> kk, bounds;                                          // host copies: the source of the asynchronous upload
+    DevBuf d_kk, d_bounds;
 };
 
 struct Wt { void* p = nullptr; std::vector<int64_t> shape; int64_t numel = 0; size_t bytes = 0; };
@@ -141,6 +151,9 @@ struct car_ctx {
     car_dpt_config dpt = {}; bool has_dpt = false;   // car_depth_configure
     std::map<int, void*> depth_pos_cache;   // token grid -> T [1 + g*g, hidden]: depth.dpt.embeddings.position_embeddings resized bilinearly
     DevBuf depth_ws;     // car_depth: the neck's feature maps, three rotating activation buffers, the fp32 map and the per-image maxima of one chunk of images
+    ResampleAxis rs_axis[2];   // car_resize: the last table set, [0] horizontal, [1] vertical
+    hipEvent_t ev_rs = nullptr;   // recorded behind the last table upload: the host copies are rewritten only after it
+    DevBuf resize_ws;    // car_resize: the uint8 intermediate between the horizontal and the vertical pass (grows on demand)
     car_t5_config t5 = {}; bool has_t5 = false;
     DevBuf t5_in;        // int32 ids [B*T] | uint8 key mask [B*T] | staging for host-side int64 inputs
     DevBuf t5_bias; int t5_bias_T = 0;   // position bias fp32 [heads][T][T] of the last sequence length

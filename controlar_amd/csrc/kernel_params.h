@@ -92,3 +92,19 @@ struct DptConvP {
     int Hi, Wi, H, W;
     int Cin, N, K, stride, relu_in, relu_out;
 };
+
+// ------------------------------------------------------------------ Pillow-exact 8-bit resampler (resample.hip; ImagingResample for modes L / RGB)
+// One pass over uint8 rows of `row_bytes` = width * C interleaved bytes; a thread owns 4 consecutive bytes of one output row.
+//   pass 0 (horizontal): output row r is source row src_y0 + r; byte e = x*C + c sums source pixels bounds[2x] .. +bounds[2x+1] of channel c with kk[x][*]
+//   pass 1 (vertical):   output row r sums source rows bounds[2r] .. +bounds[2r+1] with kk[r][*]; `src` starts at image row src_y0
+//   pass 2 (copy):       output row r is source row r
+// Each sum is (1 << 21) + sum(pixel * k) in int32, shifted right by 22 (arithmetic) and clamped to 0..255.
+// final = 0: the bytes go to `tmp` (row pitch tmp_pitch, a multiple of 4; the pad bytes are written as 0).  final = 1: to out (dense [B][rows][row_bytes])
+// and / or control (T [B][3][rows][Wo] = 2*(v/255 - 0.5), C = 1 replicated) and / or fout (fp32 [B][C][rows][Wo]: norm 0 raw, norm 1 = 2*(v/255 - 0.5)).
+struct ResampleP {
+    const unsigned char* src; long src_img; int src_pitch, src_y0, src_aligned;   // src_aligned: base, pitch and image stride are multiples of 4
+    const int* kk; const int* bounds; int ksize;
+    int B, C, rows, row_bytes, nq;                                                // nq = quads per output row
+    unsigned char* tmp; long tmp_img; int tmp_pitch;
+    unsigned char* out; void* control; float* fout; int norm, Wo, final;
+};

@@ -5,7 +5,9 @@ What sits in FRONT of the path in the reference demo is injected, because it is 
 condition extractors and the Flan-T5 encoder are upstream producers):
   * ``preprocessor(name, image, **kw) -> PIL.Image | np.ndarray`` — the reference's external ``Preprocessor`` (Canny / HED / Lineart /
     depth).  ``'No preprocess'`` (a choice of the reference UI, demo/model.py:123-124) needs none: the image IS the control map;
-    ``'Canny'`` falls back to the built-in GPU extractor (``controlar_amd.condition.CannyDetector``) when nothing is injected.
+    ``'Canny'`` falls back to the built-in GPU extractor (``controlar_amd.condition.CannyDetector``) when nothing is injected, and
+    ``'HED'`` / ``'Lineart'`` / ``'Depth'`` to the library's own extractors when they are handed over as ``hed=`` / ``lineart=`` / ``depth=``
+    (``condition.HEDdetector`` / ``LineArt`` / ``DepthEstimator`` instances).  The photo's resize in front of them runs on the GPU (``car_resize``).
   * ``text_encoder(prompts) -> (caption_embs [B,120,2048], emb_masks [B,120])`` — ``T5Embedder.get_text_embeddings`` (language/t5.py:58-79).
     A prompt may also be given directly as such a pair (precomputed features, as the training pipeline stores them).
 The rest — resize to 512x512, ``2*(x/255-0.5)``, left-padding of the caption, ``generate(..., sample_logits=True)``, ``decode_code``,
@@ -41,12 +43,15 @@ def left_pad_caption(caption_embs: torch.Tensor, emb_masks: torch.Tensor) -> Tup
 class Model:
     def __init__(self, gpt_edge: Optional[Transformer] = None, gpt_depth: Optional[Transformer] = None, vq_model: Optional[VQModel] = None,
                  text_encoder: Optional[Callable[[Sequence[str]], TextFeatures]] = None,
-                 preprocessor: Optional[Callable[..., object]] = None, device: str = "cuda"):
+                 preprocessor: Optional[Callable[..., object]] = None, device: str = "cuda", hed=None, lineart=None, depth=None):
         self.gpt = {"edge": gpt_edge, "depth": gpt_depth}
         self.vq_model = vq_model
         self.text_encoder = text_encoder
         self.preprocessor = preprocessor
         self.device = torch.device(device)
+        # the library's own extractors (condition.HEDdetector / LineArt / DepthEstimator instances, weights loaded): with one of them and no injected
+        # `preprocessor`, 'HED' / 'Lineart' / 'Depth' run on the GPU from the uint8 photo on
+        self.extractors = {"HED": hed, "Lineart": lineart, "Depth": depth}
 
     # ------------------------------------------------------------------ shared tail of both entry points (demo/model.py:127-187)
     def _run(self, kind: str, condition_img, prompt, cfg_scale, temperature, top_k, top_p, seed, control_strength) -> list:
@@ -79,28 +84,47 @@ class Model:
         samples = 255 * (samples * 0.5 + 0.5)
         return [Image.fromarray(s.permute(1, 2, 0).cpu().detach().numpy().clip(0, 255).astype(np.uint8)) for s in samples]
 
+    def _detect_input(self, image, res):
+        """The reference's external Preprocessor (demo/model.py:15,32 — not part of its repository) resizes the photo to `detect_resolution` BEFORE
+        detecting, by the rule of condition/utils.py:9-38: HWC3, then shorter side -> detect_resolution, both sides rounded to multiples of 64, Lanczos
+        when enlarging / area when shrinking.  The same rule runs here on the GPU with PIL's filters (cv2 is not available: LANCZOS / BOX are its
+        counterparts, not bit-equal to cv2.resize).  Returns the uint8 (H,W,3) tensor on the GPU."""
+        from .condition import BOX, HWC3, LANCZOS, shared_resizer
+        x = HWC3(torch.from_numpy(np.array(image.convert("RGB")))).to(self.device)
+        if res:
+            H0, W0 = x.shape[0], x.shape[1]
+            k = float(res) / min(H0, W0)
+            H1, W1 = int(np.round(H0 * k / 64.0)) * 64, int(np.round(W0 * k / 64.0)) * 64
+            if (W1, H1) != (W0, H0) and H1 > 0 and W1 > 0:
+                x = shared_resizer(self.device).on_device(x, (W1, H1), LANCZOS if k > 1 else BOX)
+        return x
+
     def _preprocess(self, name: str, image, **kw):
         if name == "No preprocess":
             return image
         if self.preprocessor is None and name == "Canny":
-            # built-in: cv2.Canny on the GPU (car_canny, condition/canny.py:6-14).  The reference's external Preprocessor (demo/model.py:15,32 — not part
-            # of its repository) resizes the photo to `detect_resolution` BEFORE detecting edges, by the rule of condition/utils.py:28-38
-            # (shorter side -> detect_resolution, both sides rounded to multiples of 64, Lanczos when enlarging / area when shrinking); the same
-            # rule is applied here with PIL's filters (cv2 is not available: LANCZOS / BOX are its counterparts, not bit-equal to cv2.resize).
+            # built-in: cv2.Canny on the GPU (car_canny, condition/canny.py:6-14) behind the detect-resolution resize (_detect_input).
             # The caller then resizes the edge map to 512x512 exactly as demo/model.py:127 does.
-            from PIL import Image
             from .condition import CannyDetector
             if getattr(self, "_canny", None) is None:
                 self._canny = CannyDetector(self.device)
-            img = image.convert("RGB")
-            res = kw.get("detect_resolution")
-            if res:
-                W0, H0 = img.size
-                k = float(res) / min(H0, W0)
-                H1, W1 = int(np.round(H0 * k / 64.0)) * 64, int(np.round(W0 * k / 64.0)) * 64
-                if (W1, H1) != (W0, H0) and H1 > 0 and W1 > 0:
-                    img = img.resize((W1, H1), Image.LANCZOS if k > 1 else Image.BOX)
-            return self._canny(np.array(img), kw.get("low_threshold", 100), kw.get("high_threshold", 200))
+            return self._canny(self._detect_input(image, kw.get("detect_resolution")), kw.get("low_threshold", 100), kw.get("high_threshold", 200))
+        ext = getattr(self, "extractors", {}).get(name) if self.preprocessor is None else None
+        if ext is not None and name == "HED":
+            # sample_t2i.py:126-128: the detector on the uint8 (1,3,H,W) photo; its 0..255 map becomes the uint8 control image
+            x = self._detect_input(image, kw.get("detect_resolution"))
+            return ext(x.permute(2, 0, 1).unsqueeze(0))[0].clamp(0, 255).to(torch.uint8).cpu().numpy()
+        if ext is not None and name == "Lineart":
+            # sample_t2i.py:129-132: the network on the float photo, 1 - y, times 255
+            x = self._detect_input(image, kw.get("detect_resolution"))
+            y = ext(x.permute(2, 0, 1).unsqueeze(0).float())
+            return ((1 - y) * 255)[0, 0].clamp(0, 255).to(torch.uint8).cpu().numpy()
+        if ext is not None and name == "Depth":
+            # sample_t2i.py:134-139: the processor's bicubic resize to 512x512 with rescale and normalise, the model, d * 255 / max
+            res = int(kw.get("detect_resolution") or 512)
+            pv = ext.preprocess(image.convert("RGB"), size=(res, res))
+            d = ext(pixel_values=pv).predicted_depth[0]
+            return (d * 255 / d.max()).clamp(0, 255).to(torch.uint8).cpu().numpy()
         if self.preprocessor is None:
             raise RuntimeError(f"Model: preprocessor '{name}' needs the preprocessor callable (the reference's external Preprocessor, demo/model.py:15,32); "
                                "'No preprocess' takes the image as the control map")

@@ -12,6 +12,11 @@ from . import _lib as L
 from .config import PathConfig
 
 
+# Image.resize filters by name -> Pillow's integer codes, which are car_resize's (NEAREST = 0 is refused by the library)
+RESAMPLE_CODES = {"nearest": 0, "lanczos": L.CAR_FILTER_LANCZOS, "bilinear": L.CAR_FILTER_BILINEAR, "bicubic": L.CAR_FILTER_BICUBIC,
+                  "box": L.CAR_FILTER_BOX, "hamming": L.CAR_FILTER_HAMMING}
+
+
 def _stream_ptr() -> int:
     return int(torch.cuda.current_stream().cuda_stream)
 
@@ -252,6 +257,35 @@ class Engine:
                     "car_canny")
         edges = edges[0] if single else edges
         return (edges, ctrl) if want_control else edges
+
+    def resize(self, img: torch.Tensor, size, resample="bicubic", box=None, want_control: bool = False, want_float=None):
+        """PIL's Image.resize(size, resample, box) on 8-bit images, bit for bit, on the GPU (car_resize).  img uint8 [B,H,W,C], [H,W,C] or [H,W], C in
+        {1, 3}; size = (W, H) as PIL orders it; resample: a name ('lanczos', 'bilinear', 'bicubic', 'box', 'hamming') or Pillow's integer code; box =
+        (x0, y0, x1, y1) in source pixels.  Returns the uint8 result in the input's layout; with want_control also the control tensor [B,3,Ho,Wo] =
+        2*(x/255-0.5) in the context's element type; with want_float ('raw' | 0: (float)x, 'norm' | 1: (x/255-0.5)/0.5) also fp32 [B,C,Ho,Wo]."""
+        filt = RESAMPLE_CODES.get(resample.lower()) if isinstance(resample, str) else int(resample)
+        if filt is None:
+            raise ValueError(f"unknown resample filter {resample!r} (one of {sorted(RESAMPLE_CODES)})")
+        if img.dim() not in (2, 3, 4):
+            raise ValueError(f"expected a uint8 image [B,H,W,C], [H,W,C] or [H,W], got {tuple(img.shape)}")
+        if img.dtype != torch.uint8:
+            raise TypeError(f"resize takes 8-bit images (torch.uint8), got {img.dtype}")
+        x = img.to(self.device)
+        x = (x[None, :, :, None] if img.dim() == 2 else x[None] if img.dim() == 3 else x).contiguous()
+        B, H, W, ch = x.shape
+        Wo, Ho = int(size[0]), int(size[1])
+        norm = None if want_float is None else {"raw": 0, "norm": 1, 0: 0, 1: 1}[want_float]
+        ok = Ho > 0 and Wo > 0                                    # a refused call allocates nothing: the library reports the reason
+        out = torch.empty(B, Ho, Wo, ch, dtype=torch.uint8, device=self.device) if ok else None
+        ctrl = torch.empty(B, 3, Ho, Wo, dtype=self.dtype, device=self.device) if (want_control and ok) else None
+        fl = torch.empty(B, ch, Ho, Wo, dtype=torch.float32, device=self.device) if (norm is not None and ok) else None
+        cbox = None if box is None else (C.c_float * 4)(*[float(v) for v in box])
+        self._check(self.lib.car_resize(self._h, C.c_void_p(x.data_ptr()), B, H, W, ch, Ho, Wo, filt, cbox,
+                                        C.c_void_p(out.data_ptr() if out is not None else 0), C.c_void_p(ctrl.data_ptr() if ctrl is not None else 0),
+                                        C.c_void_p(fl.data_ptr() if fl is not None else 0), norm or 0, C.c_void_p(_stream_ptr())), "car_resize")
+        out = out[0, :, :, 0] if img.dim() == 2 else out[0] if img.dim() == 3 else out
+        extra = tuple(t for t in (ctrl, fl) if t is not None)
+        return (out,) + extra if extra else out
 
     def load_lineart(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
         """LineArt().state_dict() names (condition/lineart.py:26-72: model0.1.weight ... model4.1.bias); the C ABI namespaces them under 'lineart.'."""

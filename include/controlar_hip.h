@@ -165,6 +165,29 @@ int car_canny(car_ctx* ctx, const uint8_t* img_hwc, int32_t B, int32_t H, int32_
               uint8_t* edges_out, void* control_out, void* stream);
 
 /*
+ * Image resize — replaces PIL's Image.resize(size, resample, box) on 8-bit images in front of every extractor (sample_t2i_MR.py:37-49,
+ * dataset/augmentation.py:8-26 center_crop_arr, sample_t2i.py:135 DPTImageProcessor, demo/model.py:127,221, condition/utils.py:28-38 resize_image).
+ * img_hwc: uint8 [B,H,W,C] (device), interleaved as car_canny takes it, C = 1 (mode L) or 3 (mode RGB).  filter: Pillow's own codes, the CAR_FILTER_*
+ * values below.  box: four floats x0, y0, x1, y1 on the HOST (the source region, 0 <= x0 < x1 <= W, 0 <= y0 < y1 <= H, fractions allowed) or NULL = the
+ * whole image.  out_hwc: uint8 [B,Ho,Wo,C] or NULL.  control_out: [B,3,Ho,Wo] in the context's element type, = 2*(x/255 - 0.5), C = 1 replicated over
+ * the three channels, ready for car_encode_control, or NULL.  float_out: fp32 [B,C,Ho,Wo] or NULL; norm 0: the raw value (float)x, what car_hed and
+ * car_lineart take; norm 1: (x/255 - 0.5)/0.5, the pixel_values car_depth takes (the same bits as 2*(x/255 - 0.5)).  Not all three NULL.  Both float
+ * tensors are evaluated in fp32 with a correctly rounded division and rounded once.
+ * The arithmetic is Pillow's ImagingResample (checked against Pillow 12.2.0): per axis a table of fixed-point taps (22 fractional bits) computed on
+ * the host in double, a horizontal pass into a uint8 intermediate — that rounding is part of the result — then a vertical pass, int32 sums; an
+ * axis whose size stays and whose box spans it is skipped, and with both skipped the result is a copy.  Integer throughout, so out_hwc is
+ * bit-identical to Pillow's for every filter, size and box.  One table pair serves the whole batch; the last pair stays in the context, keyed by
+ * (input size, box edges, output size, filter) per axis, and is uploaded on the stream when the key changes.  Works on any context (no weights
+ * needed), deterministic, batch-invariant, no host synchronisation.  Refused, with the context left usable: all outputs NULL; C other than 1 or 3
+ * (for 4 the message points at HWC3); a non-positive size or a side above 65536; NEAREST (Pillow takes another code path for it) or an unknown
+ * filter; an empty box or one outside the image.  Out of scope: modes F, I and RGBA, NEAREST, and reducing_gap.
+ */
+enum { CAR_FILTER_LANCZOS = 1, CAR_FILTER_BILINEAR = 2, CAR_FILTER_BICUBIC = 3, CAR_FILTER_BOX = 4, CAR_FILTER_HAMMING = 5 };
+int car_resize(car_ctx* ctx, const uint8_t* img_hwc, int32_t B, int32_t H, int32_t W, int32_t C,
+               int32_t Ho, int32_t Wo, int32_t filter, const float* box /* x0,y0,x1,y1 or NULL = whole image */,
+               uint8_t* out_hwc, void* control_out, float* float_out, int32_t norm, void* stream);
+
+/*
  * LineArt control extraction — replaces LineArt.forward (condition/lineart.py:26-86, default constructor: 3 residual blocks, sigmoid; callers
  * sample_t2i.py:110-113,129-132, sample_t2i_MR.py, autoregressive/test/test_t2i.py:177).  img_nchw: fp32 [B,3,H,W] (device), raw 0..255 values as the
  * reference receives them.  out: fp32 [B,1,Ho,Wo] in (0,1) or NULL; control_out: [B,3,Ho,Wo] in the context's element type, = 1 - 2*out replicated over
@@ -321,6 +344,12 @@ int car_check_errors(car_ctx* ctx);
 /* Host-only: the MFMA-fragment image of a decode linear W[N,K] (bf16 bits): chunk (rb,kb) = 64 lanes x 8 values, lane l holds
  * W[16rb + (l&15)][32kb + 8(l>>4) .. +8]; chunks ordered [rb][kb].  N % 16 == 0, K % 32 == 0. */
 int car_debug_pack_decode_weight(const float* w, int32_t N, int32_t K, uint16_t* out);
+
+/* Host-only: the coefficient table car_resize builds for one axis: input size, box edges in0 < in1 within [0, in_size], output size, filter.
+ * *ksize_out = taps per output index; kk [out_size][ksize] fixed-point taps (22 fractional bits, zero past the bound); bounds [out_size][2] =
+ * (first source index, number of taps).  max_kk: the capacity of kk in elements; non-zero when it is too small or an argument is refused. */
+int car_debug_resample_coeffs(int32_t in_size, double in0, double in1, int32_t out_size, int32_t filter,
+                              int32_t* ksize_out, int32_t* kk /* [out_size*ksize] */, int32_t* bounds /* [out_size*2] */, int64_t max_kk);
 
 /* Host-only: fp32 -> OCP e4m3fn bytes with the library's rounding (round-to-nearest-even, saturating at 448). */
 int car_debug_f32_to_e4m3(const float* in, unsigned char* out, int64_t n);
