@@ -2,9 +2,8 @@
 // DPTDepthEstimationHead) on the GPU.  Activations are NHWC in the context's element type T (bf16_t fast / float exact), accumulators fp32, the
 // final map fp32 (DPT section).  The ViT backbone and every 1x1 convolution run on gemm.hip / attn.hip / ops.hip (engine_depth.hip).
 //   dpt_patchify   fp32 NCHW pixel_values -> T patch matrix [image*token][3*16*16], k = (c, py, px) as Conv2d(3, D, 16, 16).weight flattens.
-//   dpt_conv       3x3 / pad 1 / stride 1 or 2 implicit GEMM, 128 pixels x 64 channels per block, 4 waves x (32 x 64) on
-//                  v_mfma_f32_16x16x32_bf16 / v_mfma_f32_16x16x4_f32, k in chunks of 32 through two LDS stages (the global loads of chunk k+1 fly
-//                  over the MFMAs of chunk k, one barrier per chunk).  Switches: ReLU on the input inside the gather (the pre-activation of a
+//   dpt_conv       3x3 / pad 1 / stride 1 or 2 implicit GEMM on the shared tile loop (conv_tile.h: 128 pixels x 64 channels per block, two LDS
+//                  stages).  Switches: ReLU on the input inside the gather (the pre-activation of a
 //                  residual conv unit), optional bias, up to two residual addends, ReLU on the output, and — for the head's last conv — the
 //                  32 -> 1 projection + ReLU folded into the epilogue (fp32 map out).  N need not be a multiple of 64: rows of the weight tile
 //                  beyond N are zero, their outputs are never stored.
@@ -14,10 +13,7 @@
 // No atomics anywhere and no tile crosses an image: two calls give the same bits, and image i alone gives the bits of image i in a batch.
 #include "car_common.h"
 #include "kernel_params.h"
-
-template <typename T> struct DptT;
-template <> struct DptT<bf16_t> { static constexpr int LD = 40, VE = 8; };    // LDS row stride in elements (80 B: 16-B aligned, off the 64-B period); elements per 16 B
-template <> struct DptT<float>  { static constexpr int LD = 36, VE = 4; };
+#include "conv_tile.h"
 
 // 16 bytes of T <-> fp32
 __device__ __forceinline__ void dpt_ldv(const bf16_t* p, float (&v)[8]) {
@@ -58,101 +54,29 @@ template <> __device__ __forceinline__ uint4 dpt_vrelu<bf16_t>(uint4 a) {
     return make_uint4(dpt_relu2bf(a.x), dpt_relu2bf(a.y), dpt_relu2bf(a.z), dpt_relu2bf(a.w));
 }
 
-#define DPT_CLD 68
+// The A-tile gather of dpt_conv (conv_tile.h): zero pad 1, stride 1 or 2, optionally max(x, 0).  Cin % 32 == 0: every chunk is vectors.
+template <typename T>
+struct DptGather {
+    static constexpr bool HAS_FILL = false, PARTIAL_N = true;
+    const DptConvP& p; const T* __restrict__ in;
+    __device__ __forceinline__ int cin() const { return p.Cin; }
+    __device__ __forceinline__ int stride() const { return p.stride; }
+    __device__ __forceinline__ bool inside(int iy, int ix) const { return iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi; }
+    __device__ __forceinline__ uint4 vec(int iy, int ix, int c) const {
+        const uint4 t = *(const uint4*)(in + ((long)iy * p.Wi + ix) * p.Cin + c);
+        return p.relu_in ? dpt_vrelu<T>(t) : t;
+    }
+};
+
 template <typename T>
 __global__ __launch_bounds__(256) void dpt_conv_kernel(const DptConvP p) {
-    constexpr int LD = DptT<T>::LD, VE = DptT<T>::VE, VPR = 32 / VE, NA = 128 * VPR / 256, NB = 64 * VPR / 256;
-    constexpr int ABUF = 128 * LD, BBUF = 64 * LD;
-    constexpr int STAGE_BYTES = 2 * (ABUF + BBUF) * (int)sizeof(T), CS_BYTES = 128 * DPT_CLD * 4;
-    __shared__ __attribute__((aligned(16))) char smem[STAGE_BYTES > CS_BYTES ? STAGE_BYTES : CS_BYTES];
-    T* const As = (T*)smem;                           // [2][128][LD]
-    T* const Bs = As + 2 * ABUF;                      // [2][64][LD]
-    float* const Cs = (float*)smem;                   // [128][DPT_CLD], after the k loop
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ __attribute__((aligned(16))) char smem[ConvTile128<T>::SMEM_BYTES];
+    const int tid = threadIdx.x;
     const int img = blockIdx.z, n0 = blockIdx.y * 64, m0 = blockIdx.x * 128;
     const int M = p.H * p.W;
-    const T* __restrict__ in = (const T*)p.in + (long)img * p.in_img;
-    const T* __restrict__ w = (const T*)p.w + (long)n0 * p.K;
-    int rrow[NA], rko[NA], rgy[NA], rgx[NA]; bool rok[NA];
-#pragma unroll
-    for (int v = 0; v < NA; ++v) {
-        const int vi = tid + v * 256;
-        rrow[v] = vi / VPR; rko[v] = (vi % VPR) * VE;
-        const int m = m0 + rrow[v];
-        rok[v] = m < M;
-        const int gy = rok[v] ? m / p.W : 0, gx = rok[v] ? m - gy * p.W : 0;
-        rgy[v] = gy * p.stride; rgx[v] = gx * p.stride;             // centre tap in input coordinates
-    }
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    uint4 ra[NA], rb[NB];
-    auto load_a = [&](int k0) {                     // Cin % 32 == 0: a 32-wide k chunk lies inside one tap, one 16-B vector per (row, k-slice)
-        const int tap = k0 / p.Cin, c0 = k0 - tap * p.Cin;
-        const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-#pragma unroll
-        for (int v = 0; v < NA; ++v) {
-            ra[v] = make_uint4(0u, 0u, 0u, 0u);
-            const int iy = rgy[v] + dy, ix = rgx[v] + dx;
-            if (rok[v] && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi) {
-                const uint4 t = *(const uint4*)(in + ((long)iy * p.Wi + ix) * p.Cin + c0 + rko[v]);
-                ra[v] = p.relu_in ? dpt_vrelu<T>(t) : t;
-            }
-        }
-    };
-    auto load_b = [&](int k0) {                     // rows of the 64-channel tile beyond N read as zero
-#pragma unroll
-        for (int v = 0; v < NB; ++v) rb[v] = n0 + rrow[v] < p.N ? *(const uint4*)(w + (long)rrow[v] * p.K + k0 + rko[v]) : make_uint4(0u, 0u, 0u, 0u);
-    };
-    auto stage = [&](int buf) {
-        T* A = As + buf * ABUF; T* B = Bs + buf * BBUF;
-#pragma unroll
-        for (int v = 0; v < NA; ++v) *(uint4*)&A[rrow[v] * LD + rko[v]] = ra[v];
-#pragma unroll
-        for (int v = 0; v < NB; ++v) *(uint4*)&B[rrow[v] * LD + rko[v]] = rb[v];
-    };
-    load_a(0); load_b(0);
-    stage(0);
-    __syncthreads();
-    int cur = 0;
-    for (int k0 = 0; k0 < p.K; k0 += 32) {
-        const bool more = k0 + 32 < p.K;
-        if (more) { load_a(k0 + 32); load_b(k0 + 32); }
-        const T* A = As + cur * ABUF + (32 * wv + (lane & 15)) * LD; const T* B = Bs + cur * BBUF + (lane & 15) * LD;
-        if constexpr (ET<T>::mode == 1) {
-            const bf16x8 a0 = *(const bf16x8*)&A[8 * (lane >> 4)], a1 = *(const bf16x8*)&A[16 * LD + 8 * (lane >> 4)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bf16x8 b = *(const bf16x8*)&B[16 * j * LD + 8 * (lane >> 4)];
-                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b, acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b, acc[1][j], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const float a0 = A[4 * ks + (lane >> 4)], a1 = A[16 * LD + 4 * ks + (lane >> 4)];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float b = B[16 * j * LD + 4 * ks + (lane >> 4)];
-                    acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][j], 0, 0, 0);
-                    acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][j], 0, 0, 0);
-                }
-            }
-        }
-        if (more) stage(cur ^ 1);                     // the other stage: its last readers passed the barrier that ended the previous chunk
-        __syncthreads();
-        cur ^= 1;
-    }
-    // accumulators: col = lane & 15, row = 4 * (lane >> 4) + r.  Cs overlays the stages: every wave is past the loop's last barrier.
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[(32 * wv + 16 * i + 4 * (lane >> 4) + r) * DPT_CLD + 16 * j + (lane & 15)] = acc[i][j][r];
-    __syncthreads();
+    const DptGather<T> g{p, (const T*)p.in + (long)img * p.in_img};
+    conv_tile_128x64<T>(smem, g, (const T*)p.w + (long)n0 * p.K, p.N - n0, p.K, m0, M, p.W);      // rows of the 64-channel tile beyond N read as zero
+    const float* const Cs = (const float*)smem;
     const int rows = M - m0 < 128 ? M - m0 : 128;
     T* __restrict__ out = p.out ? (T*)p.out + (long)img * p.out_img : nullptr;
     const T* __restrict__ r1 = p.res1 ? (const T*)p.res1 + (long)img * p.res1_img : nullptr;
@@ -163,7 +87,7 @@ __global__ __launch_bounds__(256) void dpt_conv_kernel(const DptConvP p) {
     for (int it = 0; it < 8; ++it) {                  // 128 rows x 16 four-channel groups; the 16 groups of a row are 16 consecutive lanes
         const int idx = tid + it * 256, row = idx >> 4, c4 = (idx & 15) * 4;
         const bool ok = row < rows && n0 + c4 < p.N;  // N % 4 == 0: a group lies inside N or outside it
-        const float4 x = *(const float4*)&Cs[row * DPT_CLD + c4];
+        const float4 x = *(const float4*)&Cs[row * CONV_CLD + c4];
         float v[4] = {x.x, x.y, x.z, x.w};
         if (ok) {
             const long o = (long)(m0 + row) * p.N + n0 + c4;
@@ -178,19 +102,10 @@ __global__ __launch_bounds__(256) void dpt_conv_kernel(const DptConvP p) {
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = ET<T>::rnd(p.relu_out && v[e] < 0.f ? 0.f : v[e]);
-            if (out) {
-                if constexpr (ET<T>::mode == 1) *(uint2*)(out + o) = make_uint2((unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16), (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16));
-                else *(float4*)(out + o) = make_float4(v[0], v[1], v[2], v[3]);
-            }
+            if (out) conv_store4(out + o, v[0], v[1], v[2], v[3]);
         }
         if (proj) {                                   // uniform over the block: every lane takes part in the shuffles
-            float s = 0.f;
-            if (ok) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) s += v[e] * ET<T>::ld(proj + n0 + c4 + e);
-            }
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            float s = conv_proj16(v[0], v[1], v[2], v[3], proj + n0 + c4, ok);
             if (row < rows && (idx & 15) == 0) { s += p.proj_bias[0]; map[m0 + row] = s > 0.f ? s : 0.f; }
         }
     }
@@ -199,7 +114,7 @@ __global__ __launch_bounds__(256) void dpt_conv_kernel(const DptConvP p) {
 // GEMM output of a ConvTranspose2d with kernel = stride = k: in [image*g*g][(ky*k + kx)*C + c] -> out [image][g*k][g*k][C]
 template <typename T>
 __global__ void dpt_shuffle_kernel(const T* __restrict__ in, T* __restrict__ out, int g, int k, int C, long nvec) {
-    constexpr int VE = DptT<T>::VE;
+    constexpr int VE = ConvT<T>::VE;
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x; const long st = (long)gridDim.x * blockDim.x;
     const int cv = C / VE, rowv = k * k * cv, gk = g * k;
     for (; i < nvec; i += st) {
@@ -212,7 +127,7 @@ __global__ void dpt_shuffle_kernel(const T* __restrict__ in, T* __restrict__ out
 // bilinear x2, align_corners = True (ATen upsample_bilinear2d): in [image][h][w][C] -> out [image][2h][2w][C]
 template <typename T>
 __global__ void dpt_up2_kernel(const T* __restrict__ in, T* __restrict__ out, int h, int w, int C, long nvec) {
-    constexpr int VE = DptT<T>::VE;
+    constexpr int VE = ConvT<T>::VE;
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x; const long st = (long)gridDim.x * blockDim.x;
     const int cv = C / VE, Ho = 2 * h, Wo = 2 * w;
     const float sh = (float)(h - 1) / (float)(Ho - 1), sw = (float)(w - 1) / (float)(Wo - 1);

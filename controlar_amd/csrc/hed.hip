@@ -2,20 +2,15 @@
 // Activations are NHWC in the context's element type T (bf16_t fast / float exact), accumulators fp32 (HED section).
 //   hed_to_nhwc    fp32 NCHW image (raw 0..255 values) minus norm[c] -> T NHWC.  The subtraction lives here and nowhere else: the first conv pads
 //                  the DIFFERENCE with zeros, so norm cannot move into that conv's bias.
-//   hed_conv       3x3 / stride 1 / zero pad implicit GEMM, 128 pixels x 64 channels per block, 4 waves x (32 x 64) on v_mfma_f32_16x16x32_bf16 /
-//                  v_mfma_f32_16x16x4_f32, k in chunks of 32 through two LDS stages (the global loads of chunk k+1 fly over the MFMAs of chunk k, one
-//                  barrier per chunk).  pool = 1 reads the input through a 2x2 / stride-2 max-pool in the gather (floor: an odd last row or column is
-//                  never addressed).  The epilogue adds the bias, applies ReLU, stores T, and — in the last conv of a block — reduces the T-rounded
+//   hed_conv       3x3 / stride 1 / zero pad implicit GEMM on the shared tile loop (conv_tile.h: 128 pixels x 64 channels per block, two LDS stages).
+//                  pool = 1 reads the input through a 2x2 / stride-2 max-pool in the gather (floor: an odd last row or column is never addressed).  The epilogue adds the bias, applies ReLU, stores T, and — in the last conv of a block — reduces the T-rounded
 //                  64-channel slice against projection.weight into an fp32 partial per (channel block, pixel).
 //   hed_fuse       per output pixel: the five side maps (partials summed in channel-block order + bias) up-sampled bilinearly as ATen does
 //                  (align_corners = False), mean in stack order, sigmoid, x255, clamp; optional control tensor 2*(edge/255 - 0.5) on three channels.
 // No atomics anywhere and no tile crosses an image: two calls give the same bits, and image i alone gives the bits of image i in a batch.
 #include "car_common.h"
 #include "kernel_params.h"
-
-template <typename T> struct HedT;
-template <> struct HedT<bf16_t> { static constexpr int LD = 40, VE = 8; };    // LDS row stride in elements (80 B: 16-B aligned, off the 64-B period); elements per 16 B
-template <> struct HedT<float>  { static constexpr int LD = 36, VE = 4; };
+#include "conv_tile.h"
 
 template <typename T>
 __global__ void hed_to_nhwc_kernel(const float* __restrict__ img, const float* __restrict__ norm, T* __restrict__ out, long HW, long n) {
@@ -41,119 +36,48 @@ template <> __device__ __forceinline__ uint4 hed_vmax<bf16_t>(uint4 a, uint4 b) 
     return make_uint4(hed_max2bf(a.x, b.x), hed_max2bf(a.y, b.y), hed_max2bf(a.z, b.z), hed_max2bf(a.w, b.w));
 }
 
-#define HED_CLD 68
+// The A-tile gather of hed_conv (conv_tile.h): zero pad 1, optionally through the 2x2 / stride-2 max-pool, and the element-wise path of Cin = 3.
+template <typename T>
+struct HedGather {
+    static constexpr bool HAS_FILL = true, PARTIAL_N = false;      // N % 64 == 0
+    const HedConvP& p; const T* __restrict__ in;
+    __device__ __forceinline__ int cin() const { return p.Cin; }
+    __device__ __forceinline__ int stride() const { return 1; }
+    __device__ __forceinline__ bool vectors() const { return (p.Cin & 31) == 0; }
+    __device__ __forceinline__ bool inside(int iy, int ix) const { return iy >= 0 && iy < p.H && ix >= 0 && ix < p.W; }
+    __device__ __forceinline__ uint4 vec(int iy, int ix, int c) const {
+        if (p.pool) {                                 // (2iy+1, 2ix+1) <= (Hi-1, Wi-1) because H = Hi/2, W = Wi/2 (floor)
+            const T* s = in + ((long)(2 * iy) * p.Wi + 2 * ix) * p.Cin + c;
+            const uint4 t0 = *(const uint4*)s, t1 = *(const uint4*)(s + p.Cin);
+            const uint4 t2 = *(const uint4*)(s + (long)p.Wi * p.Cin), t3 = *(const uint4*)(s + (long)p.Wi * p.Cin + p.Cin);
+            return hed_vmax<T>(hed_vmax<T>(t0, t1), hed_vmax<T>(t2, t3));
+        }
+        return *(const uint4*)(in + ((long)iy * p.Wi + ix) * p.Cin + c);
+    }
+    __device__ __forceinline__ void fill(T* A, int k0, int m0, int M, int tid) const {       // Cin = 3 (block1.convs.0, never pooled): zero beyond K
+        constexpr int LD = ConvT<T>::LD;
+        for (int e = tid; e < 128 * 32; e += 256) {
+            const int row = e >> 5, kk = e & 31, k = k0 + kk, m = m0 + row;
+            T val = (T)0;
+            if (k < p.K && m < M) {
+                const int tap = k / p.Cin, ci = k - tap * p.Cin, gy = m / p.W, gx = m - gy * p.W;
+                const int iy = gy + tap / 3 - 1, ix = gx + tap % 3 - 1;
+                if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) val = in[((long)iy * p.Wi + ix) * p.Cin + ci];
+            }
+            A[row * LD + kk] = val;
+        }
+    }
+};
+
 template <typename T>
 __global__ __launch_bounds__(256) void hed_conv_kernel(const HedConvP p) {
-    constexpr int LD = HedT<T>::LD, VE = HedT<T>::VE, VPR = 32 / VE, NA = 128 * VPR / 256, NB = 64 * VPR / 256;
-    constexpr int ABUF = 128 * LD, BBUF = 64 * LD;
-    constexpr int STAGE_BYTES = 2 * (ABUF + BBUF) * (int)sizeof(T), CS_BYTES = 128 * HED_CLD * 4;
-    __shared__ __attribute__((aligned(16))) char smem[STAGE_BYTES > CS_BYTES ? STAGE_BYTES : CS_BYTES];
-    T* const As = (T*)smem;                           // [2][128][LD]
-    T* const Bs = As + 2 * ABUF;                      // [2][64][LD]
-    float* const Cs = (float*)smem;                   // [128][HED_CLD], after the k loop
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ __attribute__((aligned(16))) char smem[ConvTile128<T>::SMEM_BYTES];
+    const int tid = threadIdx.x;
     const int img = blockIdx.z, n0 = blockIdx.y * 64, m0 = blockIdx.x * 128;
     const int M = p.H * p.W;
-    const T* __restrict__ in = (const T*)p.in + (long)img * p.in_img;
-    const T* __restrict__ w = (const T*)p.w + (long)n0 * p.Kp;
-    int rrow[NA], rko[NA], rgy[NA], rgx[NA]; bool rok[NA];
-#pragma unroll
-    for (int v = 0; v < NA; ++v) {
-        const int vi = tid + v * 256;
-        rrow[v] = vi / VPR; rko[v] = (vi % VPR) * VE;
-        const int m = m0 + rrow[v];
-        rok[v] = m < M;
-        rgy[v] = rok[v] ? m / p.W : 0; rgx[v] = rok[v] ? m - rgy[v] * p.W : 0;
-    }
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bool fast = (p.Cin & 31) == 0;
-    uint4 ra[NA], rb[NB];
-    auto load_a = [&](int k0) {                     // Cin % 32 == 0: a 32-wide k chunk lies inside one tap, one 16-B vector per (row, k-slice)
-        const int tap = k0 / p.Cin, c0 = k0 - tap * p.Cin;
-        const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-#pragma unroll
-        for (int v = 0; v < NA; ++v) {
-            ra[v] = make_uint4(0u, 0u, 0u, 0u);
-            const int iy = rgy[v] + dy, ix = rgx[v] + dx;
-            if (rok[v] && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) {
-                if (p.pool) {                         // (2iy+1, 2ix+1) <= (Hi-1, Wi-1) because H = Hi/2, W = Wi/2 (floor)
-                    const T* s = in + ((long)(2 * iy) * p.Wi + 2 * ix) * p.Cin + c0 + rko[v];
-                    const uint4 t0 = *(const uint4*)s, t1 = *(const uint4*)(s + p.Cin);
-                    const uint4 t2 = *(const uint4*)(s + (long)p.Wi * p.Cin), t3 = *(const uint4*)(s + (long)p.Wi * p.Cin + p.Cin);
-                    ra[v] = hed_vmax<T>(hed_vmax<T>(t0, t1), hed_vmax<T>(t2, t3));
-                } else ra[v] = *(const uint4*)(in + ((long)iy * p.Wi + ix) * p.Cin + c0 + rko[v]);
-            }
-        }
-    };
-    auto load_b = [&](int k0) {
-#pragma unroll
-        for (int v = 0; v < NB; ++v) rb[v] = *(const uint4*)(w + (long)rrow[v] * p.Kp + k0 + rko[v]);
-    };
-    auto stage = [&](int k0, int buf) {
-        T* A = As + buf * ABUF; T* B = Bs + buf * BBUF;
-        if (fast) {
-#pragma unroll
-            for (int v = 0; v < NA; ++v) *(uint4*)&A[rrow[v] * LD + rko[v]] = ra[v];
-        } else {                                      // Cin = 3 (block1.convs.0, never pooled): element-wise gather, zero beyond K
-            for (int e = tid; e < 128 * 32; e += 256) {
-                const int row = e >> 5, kk = e & 31, k = k0 + kk, m = m0 + row;
-                T val = (T)0;
-                if (k < p.K && m < M) {
-                    const int tap = k / p.Cin, ci = k - tap * p.Cin, gy = m / p.W, gx = m - gy * p.W;
-                    const int iy = gy + tap / 3 - 1, ix = gx + tap % 3 - 1;
-                    if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) val = in[((long)iy * p.Wi + ix) * p.Cin + ci];
-                }
-                A[row * LD + kk] = val;
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < NB; ++v) *(uint4*)&B[rrow[v] * LD + rko[v]] = rb[v];
-    };
-    if (fast) load_a(0);
-    load_b(0);
-    stage(0, 0);
-    __syncthreads();
-    int cur = 0;
-    for (int k0 = 0; k0 < p.Kp; k0 += 32) {
-        const bool more = k0 + 32 < p.Kp;
-        if (more) { if (fast) load_a(k0 + 32); load_b(k0 + 32); }
-        const T* A = As + cur * ABUF + (32 * wv + (lane & 15)) * LD; const T* B = Bs + cur * BBUF + (lane & 15) * LD;
-        if constexpr (ET<T>::mode == 1) {
-            const bf16x8 a0 = *(const bf16x8*)&A[8 * (lane >> 4)], a1 = *(const bf16x8*)&A[16 * LD + 8 * (lane >> 4)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bf16x8 b = *(const bf16x8*)&B[16 * j * LD + 8 * (lane >> 4)];
-                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b, acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b, acc[1][j], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const float a0 = A[4 * ks + (lane >> 4)], a1 = A[16 * LD + 4 * ks + (lane >> 4)];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float b = B[16 * j * LD + 4 * ks + (lane >> 4)];
-                    acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][j], 0, 0, 0);
-                    acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][j], 0, 0, 0);
-                }
-            }
-        }
-        if (more) stage(k0 + 32, cur ^ 1);            // the other stage: its last readers passed the barrier that ended the previous chunk
-        __syncthreads();
-        cur ^= 1;
-    }
-    // accumulators: col = lane & 15, row = 4 * (lane >> 4) + r.  Cs overlays the stages: every wave is past the loop's last barrier.
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cs[(32 * wv + 16 * i + 4 * (lane >> 4) + r) * HED_CLD + 16 * j + (lane & 15)] = acc[i][j][r];
-    __syncthreads();
+    const HedGather<T> g{p, (const T*)p.in + (long)img * p.in_img};
+    conv_tile_128x64<T>(smem, g, (const T*)p.w + (long)n0 * p.Kp, 64, p.Kp, m0, M, p.W);
+    const float* const Cs = (const float*)smem;
     const int rows = M - m0 < 128 ? M - m0 : 128;
     T* __restrict__ out = (T*)p.out + (long)img * p.out_img;
     const T* __restrict__ proj = (const T*)p.proj;
@@ -162,24 +86,14 @@ __global__ __launch_bounds__(256) void hed_conv_kernel(const HedConvP p) {
     for (int it = 0; it < 8; ++it) {                  // 128 rows x 16 four-channel groups; the 16 groups of a row are 16 consecutive lanes
         const int idx = tid + it * 256, row = idx >> 4, c4 = (idx & 15) * 4;
         const bool ok = row < rows;
-        const float4 x = *(const float4*)&Cs[row * HED_CLD + c4];
+        const float4 x = *(const float4*)&Cs[row * CONV_CLD + c4];
         const float4 b = *(const float4*)&p.bias[n0 + c4];
         float v[4] = {x.x + b.x, x.y + b.y, x.z + b.z, x.w + b.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = ET<T>::rnd(v[e] > 0.f ? v[e] : 0.f);
-        if (ok) {
-            T* o = out + (long)(m0 + row) * p.N + n0 + c4;
-            if constexpr (ET<T>::mode == 1) *(uint2*)o = make_uint2((unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16), (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16));
-            else *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);
-        }
+        if (ok) conv_store4(out + (long)(m0 + row) * p.N + n0 + c4, v[0], v[1], v[2], v[3]);
         if (part) {                                   // uniform over the block: every lane takes part in the shuffles
-            float s = 0.f;
-            if (ok) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) s += v[e] * ET<T>::ld(proj + n0 + c4 + e);
-            }
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            const float s = conv_proj16(v[0], v[1], v[2], v[3], proj + n0 + c4, ok);
             if (ok && (idx & 15) == 0) part[m0 + row] = s;
         }
     }

@@ -2,7 +2,7 @@
 // Activations are NHWC in the context's element type T (bf16_t fast / float exact); every convolution in front of an InstanceNorm keeps its raw
 // fp32 accumulators until they are normalised (LineArt section).
 //   la_to_nhwc     fp32 NCHW photo (raw 0..255 values) -> T NHWC
-//   la_conv        implicit GEMM, 64 pixels x 64 channels per block, 4 waves x (16 x 64) on v_mfma_f32_16x16x32_bf16 / v_mfma_f32_16x16x4_f32.
+//   la_conv        implicit GEMM, 64 pixels x 64 channels per block, 4 waves x (16 x 64) on the MFMA step of conv_tile.h, around a single-stage loop.
 //                  The A tile is gathered into LDS k-chunk by k-chunk through the tap table of LaConvP: reflection is an index map of that gather,
 //                  zero padding a zero fill, stride 2 and the four parity phases of a transposed convolution are (stride, os, py, px).  The epilogue
 //                  stores the fp32 tile and its per-channel (mean, M2) over the tile's valid rows — tiles never cross an image.
@@ -13,10 +13,7 @@
 // No atomics anywhere: two calls give the same bits, and image i alone gives the bits of image i in a batch.
 #include "car_common.h"
 #include "kernel_params.h"
-
-template <typename T> struct LaT;
-template <> struct LaT<bf16_t> { static constexpr int LD = 40, VE = 8; };     // LDS row stride in elements (80 B: 16-B aligned, off the 64-B period); elements per 16 B
-template <> struct LaT<float>  { static constexpr int LD = 36, VE = 4; };
+#include "conv_tile.h"
 
 template <typename T>
 __global__ void la_to_nhwc_kernel(const float* __restrict__ img, T* __restrict__ out, long HW, long n) {
@@ -29,30 +26,22 @@ __global__ void la_to_nhwc_kernel(const float* __restrict__ img, T* __restrict__
 
 __device__ __forceinline__ int la_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 
-#define LA_CLD 68
 template <typename T>
 __global__ __launch_bounds__(256) void la_conv_kernel(const LaConvP p) {
-    constexpr int LD = LaT<T>::LD, VE = LaT<T>::VE, VPR = 32 / VE, NV = 64 * VPR / 256;
+    constexpr int LD = ConvT<T>::LD, NV = 64 * (32 / ConvT<T>::VE) / 256;
     __shared__ __attribute__((aligned(16))) T As[64 * LD];
     __shared__ __attribute__((aligned(16))) T Bs[64 * LD];
-    __shared__ __attribute__((aligned(16))) float Cs[64 * LA_CLD];
+    __shared__ __attribute__((aligned(16))) float Cs[64 * CONV_CLD];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int img = blockIdx.z, tile = blockIdx.x, n0 = blockIdx.y * 64;
     const int Mg = p.Hg * p.Wg, m0 = tile * 64;
     const T* __restrict__ in = (const T*)p.in + (long)img * p.in_img;
     const T* __restrict__ w = (const T*)p.w + (long)n0 * p.Kp;
     int rrow[NV], rko[NV], rgy[NV], rgx[NV]; bool rok[NV];
+    conv_rows<T, NV>(tid, m0, Mg, p.Wg, rrow, rko, rgy, rgx, rok);
+    f32x4 acc[1][4];
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int vi = tid + v * 256;
-        rrow[v] = vi / VPR; rko[v] = (vi % VPR) * VE;
-        const int m = m0 + rrow[v];
-        rok[v] = m < Mg;
-        rgy[v] = rok[v] ? m / p.Wg : 0; rgx[v] = rok[v] ? m - rgy[v] * p.Wg : 0;
-    }
-    f32x4 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const bool fast = (p.Cin & 31) == 0;
     // register staging: the global loads of chunk k+1 are issued before the MFMAs of chunk k
     uint4 ra[NV], rb[NV];
@@ -96,31 +85,10 @@ __global__ __launch_bounds__(256) void la_conv_kernel(const LaConvP p) {
         for (int v = 0; v < NV; ++v) *(uint4*)&Bs[rrow[v] * LD + rko[v]] = rb[v];
         __syncthreads();
         if (k0 + 32 < p.Kp) { if (fast) load_a(k0 + 32); load_b(k0 + 32); }
-        if constexpr (ET<T>::mode == 1) {
-            const bf16x8 a = *(const bf16x8*)&As[(16 * wv + (lane & 15)) * LD + 8 * (lane >> 4)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bf16x8 b = *(const bf16x8*)&Bs[(16 * j + (lane & 15)) * LD + 8 * (lane >> 4)];
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[j], 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const float a = As[(16 * wv + (lane & 15)) * LD + 4 * ks + (lane >> 4)];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float b = Bs[(16 * j + (lane & 15)) * LD + 4 * ks + (lane >> 4)];
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[j], 0, 0, 0);
-                }
-            }
-        }
+        conv_mfma_step<T, 1>(As + (16 * wv + (lane & 15)) * LD, Bs + (lane & 15) * LD, lane, acc);
         __syncthreads();
     }
-    // accumulators: col = lane & 15, row = 4 * (lane >> 4) + r
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Cs[(16 * wv + 4 * (lane >> 4) + r) * LA_CLD + 16 * j + (lane & 15)] = acc[j][r];
+    conv_spill<1>(Cs, 16 * wv, lane, acc);
     __syncthreads();
     const int rows = Mg - m0 < 64 ? Mg - m0 : 64;
     float* __restrict__ raw = p.raw + (long)img * p.raw_img;
@@ -129,15 +97,15 @@ __global__ __launch_bounds__(256) void la_conv_kernel(const LaConvP p) {
         if (row < rows) {
             const int m = m0 + row, gy = m / p.Wg, gx = m - gy * p.Wg;
             const long o = ((long)(gy * p.os + p.py) * p.Wout + (gx * p.os + p.px)) * p.N + n0 + c4;
-            *(float4*)&raw[o] = *(const float4*)&Cs[row * LA_CLD + c4];
+            *(float4*)&raw[o] = *(const float4*)&Cs[row * CONV_CLD + c4];
         }
     }
     if (tid < 64) {                                   // (mean, M2) of this tile's column, two passes over the fp32 tile, fixed order
         float s = 0.f;
-        for (int r = 0; r < rows; ++r) s += Cs[r * LA_CLD + tid];
+        for (int r = 0; r < rows; ++r) s += Cs[r * CONV_CLD + tid];
         const float mean = s / (float)rows;
         float m2 = 0.f;
-        for (int r = 0; r < rows; ++r) { const float d = Cs[r * LA_CLD + tid] - mean; m2 += d * d; }
+        for (int r = 0; r < rows; ++r) { const float d = Cs[r * CONV_CLD + tid] - mean; m2 += d * d; }
         const long slot = (long)img * p.tiles_img + p.tile0 + tile;
         ((float2*)p.part)[slot * p.N + n0 + tid] = make_float2(mean, m2);
         if (tid == 0 && blockIdx.y == 0) p.cnt[slot] = rows;

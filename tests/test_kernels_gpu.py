@@ -44,3 +44,15 @@ def test_fp8_decode_linears_against_a_reference_on_identical_codes():
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
     assert "FAIL" not in out.stdout
+
+
+def test_nhwc_conv_kernels_against_exact_integer_references():
+    """hed.hip, dpt.hip, lineart.hip (experiments/nhwc_conv_check.hip, quick mode): car_launch_hed_conv, car_launch_dpt_conv and car_launch_la_conv called directly on
+    small-integer operands, where every product and sum is exact in fp32, so the expected output has no tolerance — fp32 mode bit-equal to the host's integer
+    convolution, bf16 mode to its bf16 rounding, side partials and the DPT map to the exact sums of the rounded channels.  Two images per case, both modes, two runs
+    with equal bits; partial / tail / exact tiles, the pool over an odd map, the Cin = 3 element-wise gather, a half-masked channel tile, stride 2 on odd and even
+    maps, residual addends, the folded projection, reflection, a transposed-conv phase; every refusal of the launchers returns hipErrorInvalidValue."""
+    exe = _build("nhwc_conv_check")
+    out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
+    assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
