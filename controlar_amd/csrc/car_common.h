@@ -121,4 +121,6 @@ struct GemmP {
     float* gn_part;       // conv3_halo64_kernel only (car_conv3_halo64_ok): if set, the epilogue also writes the GroupNorm stage-1 partials of its OUTPUT
                           // tensor — per (image, 16x16 tile, channel) sum and sum of squares of the stored bf16 values, layout [B][Ho*Wo/256][2][N] =
                           // what gn_partial_vec_kernel writes with one 256-pixel chunk per tile — so the next GroupNorm skips its read-only pass
+    int split3;           // fp32 mode only (car_config.vq_split_bf16): take gemm_f32s_kernel (gemm_split.hip) where car_gemm_split_ok holds — each fp32 operand
+                          // as two bf16 numbers, three bf16 MFMAs per product; a call that is not eligible runs the exact fp32 kernels as if the flag were 0
 };

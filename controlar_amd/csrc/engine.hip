@@ -38,6 +38,8 @@ extern "C" int car_create(car_ctx** out, const car_config* cfg) {
     if (cfg->decode_weight_fp8 && (cfg->mode != CAR_BF16 || cfg->dim % 64 || cfg->ffn_hidden % 64)) {
         g_create_err = "car_create: decode_weight_fp8 needs CAR_BF16 mode and dim, ffn_hidden multiples of 64"; return -1; }
     if (cfg->kv_cache_fp8 && cfg->mode != CAR_BF16) { g_create_err = "car_create: kv_cache_fp8 exists only in CAR_BF16 mode (the exact mode is the parity path)"; return -1; }
+    if (cfg->vq_split_bf16 != 0 && cfg->vq_split_bf16 != 1) { g_create_err = "car_create: vq_split_bf16 must be 0 or 1"; return -1; }
+    if (cfg->vq_split_bf16 && cfg->mode != CAR_F32) { g_create_err = "car_create: vq_split_bf16 exists only in the fp32 mode (the bf16 mode decodes on bf16 operands already)"; return -1; }
     if (cfg->vit_hidden % cfg->vit_heads != 0 || (cfg->vit_hidden / cfg->vit_heads) % 32) { g_create_err = "car_create: ViT head_dim must be a multiple of 32"; return -1; }
     int g = (int)std::lround(std::sqrt((double)cfg->block_size));
     if (g * g != cfg->block_size) { g_create_err = "car_create: block_size must be a square (gpt_t2i.py:352)"; return -1; }

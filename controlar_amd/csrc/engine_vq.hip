@@ -9,22 +9,29 @@ struct VqOps {
     // epilogue (GemmP::gn_part -> ws[8], the layout of gn_partial_vec_kernel), and a GroupNorm whose input is that very tensor skips its read-only pass.
     // `part_of` = the tensor whose partials ws[8] currently holds (null: none); every other writer of a tensor clears it.
     mutable const void* part_of = nullptr;
+    // car_config.vq_split_bf16 (car_vq_decode in fp32 mode only; car_vq_encode leaves it 0): the GEMM-shaped layers ask for the split-bf16 kernel (GemmP::split3,
+    // gemm_split.hip), which car_launch_gemm takes wherever its predicate holds.  `rc`: the first launch the launcher refused for good (reported by the entry).
+    int split3 = 0;
+    mutable int rc = 0;
+    void launch(int amode, const GemmP& q) const { const int r = car_launch_gemm(mode, amode, &q, st); if (r != 0 && rc == 0) rc = r; }
     void conv3(const void* x, void* y, const std::string& name, int nb, int Ho, int Wo, int Cin, int Cout, int ups, const void* R, int amode = AMODE_CONV3) const {
         GemmP q = gp(x, 0, Wp(c, name + ".weight"), 9 * (long)Cin, y, Cout, nb * Ho * Wo, Cout, 9 * Cin);
         q.bias = Wp(c, name + ".bias"); q.bias_mode = BIAS_N; q.Ho = Ho; q.Wo = Wo; q.Cin = Cin; q.ups = ups; q.R = R; q.ldr = Cout;
         q.patch = 1;        // 16x16 spatial patch order of the GEMM rows where the launcher can use it (bf16, Ho and Wo multiples of 16)
+        q.split3 = split3;
         part_of = nullptr;
         if (amode == AMODE_CONV3 && car_conv3_halo64_ok(mode, &q) && Cout <= 512) { q.gn_part = (float*)c->ws[8].p; part_of = y; }
-        if (car_launch_gemm(mode, amode, &q, st) != 0) {      // the launcher refused the fused partials (cannot happen after the same predicate said yes): plain conv,
-            q.gn_part = nullptr; part_of = nullptr;            // and the next GroupNorm runs its own stage 1
-            (void)car_launch_gemm(mode, amode, &q, st);
-        }
+        if (q.gn_part && car_launch_gemm(mode, amode, &q, st) != 0) {      // the launcher refused the fused partials (cannot happen after the same predicate said yes): plain conv,
+            q.gn_part = nullptr; part_of = nullptr;                        // and the next GroupNorm runs its own stage 1
+            launch(amode, q);
+        } else if (!q.gn_part) launch(amode, q);
     }
     void conv1(const void* x, void* y, const std::string& name, int M, int Cin, int Cout, const void* R) const {
         GemmP q = gp(x, Cin, Wp(c, name + ".weight"), Cin, y, Cout, M, Cout, Cin);
         q.bias = Wp(c, name + ".bias"); q.bias_mode = BIAS_N; q.R = R; q.ldr = Cout;
+        q.split3 = split3;
         part_of = nullptr;
-        car_launch_gemm(mode, AMODE_PLAIN, &q, st);
+        launch(AMODE_PLAIN, q);
     }
     void gn(const void* x, void* y, const std::string& name, int nb, int HW, int C, int swish) const {
         const int have = (part_of != nullptr && part_of == x) ? 1 : 0;
@@ -48,10 +55,10 @@ struct VqOps {
                 void* qb = c->ws[7].p; void* kb = off(qb, (size_t)nb * HW * C, e); void* vb = off(qb, (size_t)2 * nb * HW * C, e);
                 conv1(t1, qb, it.name + ".q", nb * HW, C, C, nullptr); conv1(t1, kb, it.name + ".k", nb * HW, C, C, nullptr); conv1(t1, vb, it.name + ".v", nb * HW, C, C, nullptr);
                 float* S = (float*)c->ws[4].p;
-                { GemmP q = gp(qb, C, kb, C, S, HW, HW, HW, C); q.alpha = 1.0f / std::sqrt((float)C); q.out_f32 = 1; q.nb0 = nb; q.sA0 = (long)HW * C; q.sW0 = (long)HW * C; q.sC0 = (long)HW * HW; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
+                { GemmP q = gp(qb, C, kb, C, S, HW, HW, HW, C); q.alpha = 1.0f / std::sqrt((float)C); q.out_f32 = 1; q.nb0 = nb; q.sA0 = (long)HW * C; q.sW0 = (long)HW * C; q.sC0 = (long)HW * HW; q.split3 = split3; launch(AMODE_PLAIN, q); }
                 car_launch_softmax(mode, S, HW, c->ws[5].p, Tp, (long)nb * HW, HW, 0, nullptr, 0, 0, st);
                 car_launch_transpose_pad(mode, vb, C, (long)HW * C, c->ws[6].p, nb, HW, Tp, C, st);
-                { GemmP q = gp(c->ws[5].p, Tp, c->ws[6].p, Tp, t2, C, HW, C, Tp); q.nb0 = nb; q.sA0 = (long)HW * Tp; q.sW0 = (long)C * Tp; q.sC0 = (long)HW * C; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
+                { GemmP q = gp(c->ws[5].p, Tp, c->ws[6].p, Tp, t2, C, HW, C, Tp); q.nb0 = nb; q.sA0 = (long)HW * Tp; q.sW0 = (long)C * Tp; q.sC0 = (long)HW * C; q.split3 = split3; launch(AMODE_PLAIN, q); }
                 conv1(t2, x, it.name + ".proj_out", nb * HW, C, C, x);
             } else if (it.kind == 2) {
                 Hc *= 2; Wc *= 2;
@@ -137,6 +144,7 @@ extern "C" int car_vq_decode(car_ctx* c, const int32_t* tokens, int32_t B, int32
     NEED(c, c->ws[9], (size_t)CH * 32 * 2 * 4 + 64);          // GN stats
     fence_in(c, caller);
     VqOps ops{c, mode, e, st};
+    ops.split3 = (mode == CAR_F32 && g.vq_split_bf16) ? 1 : 0;
     for (int b0 = 0; b0 < B; b0 += CH) {
         const int nb = (B - b0) < CH ? (B - b0) : CH;
         void *x = c->ws[0].p, *t1 = c->ws[1].p, *t2 = c->ws[2].p, *t3 = c->ws[3].p;
@@ -151,5 +159,6 @@ extern "C" int car_vq_decode(car_ctx* c, const int32_t* tokens, int32_t B, int32
     }
     fence_out(c, caller);
     HIPCHK(c, hipGetLastError());
+    if (ops.rc) FAIL(c, "car_vq_decode: a GEMM launch was refused (code %d)", ops.rc);
     return 0;
 }

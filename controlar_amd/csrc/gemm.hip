@@ -7,69 +7,9 @@
 //     with zero padding and an optional fused nearest x2 upsample (vq_model.py:375-379).
 // The epilogue reproduces the reference's rounding points (one rounding per torch op).
 #include "car_common.h"
+#include "gemm_gather.h"
 #include <cstdio>
 #include <cstdlib>
-
-template <typename T>
-__device__ __forceinline__ float epi_value(const GemmP& p, const T* bias, const T* scale, const T* R, long zR, int m, long mrow, int n, float v) {
-    v *= p.alpha;
-    if (p.bias_mode == BIAS_N) v += ET<T>::ld(bias + n);
-    else if (p.bias_mode == BIAS_M) v += ET<T>::ld(bias + m);
-    v = ET<T>::rnd(v);
-    if (p.act == ACT_GELU_ERF) v = ET<T>::rnd(gelu_erf_f(v));
-    else if (p.act == ACT_GELU_TANH) v = ET<T>::rnd(gelu_tanh_f(v));
-    else if (p.act == ACT_SILU) v = ET<T>::rnd(silu_f(v));
-    if (scale) v = ET<T>::rnd(v * ET<T>::ld(scale + n));
-    if (R) v = ET<T>::rnd(v + ET<T>::ld(R + zR + mrow * p.ldr + n));
-    return v;
-}
-
-// ---- A-operand row descriptor (per thread, constant over the K loop)
-struct ARow { long base; int y, x; bool ok; };
-
-struct Geo { int M, Cin, Ho, Wo, ups; long lda; int patch; };
-// patch order: m = ((b * (Ho/16) + ty) * (Wo/16) + tx) * 256 + py * 16 + px  ->  pixel (b, ty*16 + py, tx*16 + px)
-__device__ inline void patch_decode(int Ho, int Wo, int m, int& b, int& y, int& x) {
-    const int tw = Wo >> 4, th = Ho >> 4, tile = m >> 8, within = m & 255;
-    b = tile / (tw * th); const int t2 = tile - b * (tw * th), ty = t2 / tw, tx = t2 - ty * tw;
-    y = ty * 16 + (within >> 4); x = tx * 16 + (within & 15);
-}
-// row of C / R that GEMM row m addresses (the NHWC pixel index under patch order, m itself otherwise)
-__device__ __forceinline__ long out_row(const GemmP& p, int m) {
-    if (!p.patch) return m;
-    int b, y, x; patch_decode(p.Ho, p.Wo, m, b, y, x);
-    return ((long)b * p.Ho + y) * p.Wo + x;
-}
-template <int AMODE>
-__device__ inline ARow make_arow(const Geo p, int m) {
-    ARow r; r.ok = m < p.M; r.base = 0; r.y = 0; r.x = 0;
-    if (AMODE == AMODE_PLAIN) { r.base = (long)m * p.lda; }
-    else {
-        const int hw = p.Ho * p.Wo;
-        int b = m / hw; const int rem = m - b * hw;
-        r.y = rem / p.Wo; r.x = rem - r.y * p.Wo;
-        if (AMODE == AMODE_CONV3 && p.patch) patch_decode(p.Ho, p.Wo, m, b, r.y, r.x);
-        if (AMODE == AMODE_CONV3S2) r.base = (long)b * (p.Ho * 2) * (p.Wo * 2);
-        else r.base = (long)b * (p.Ho >> p.ups) * (p.Wo >> p.ups);   // in pixels
-    }
-    return r;
-}
-// element offset of A[m, k] (k multiple of the chunk width), or -1 if the chunk is zero padding
-template <int AMODE>
-__device__ inline long a_off(const Geo p, const ARow r, int k) {
-    if (!r.ok) return -1;
-    if (AMODE == AMODE_PLAIN) return r.base + k;
-    const int tap = k / p.Cin, c = k - tap * p.Cin;
-    if (AMODE == AMODE_CONV3S2) {
-        // Downsample (vq_model.py:382-396): F.pad(x, (0,1,0,1)) then conv3x3 stride 2, no padding: taps (2y+ty, 2x+tx), zero past the edge
-        const int Hin = p.Ho * 2, Win = p.Wo * 2, yy = 2 * r.y + tap / 3, xx = 2 * r.x + tap % 3;
-        if (yy >= Hin || xx >= Win) return -1;
-        return (r.base + (long)yy * Win + xx) * p.Cin + c;
-    }
-    const int yy = r.y + tap / 3 - 1, xx = r.x + tap % 3 - 1;
-    if (yy < 0 || yy >= p.Ho || xx < 0 || xx >= p.Wo) return -1;
-    return (r.base + (long)(yy >> p.ups) * (p.Wo >> p.ups) + (xx >> p.ups)) * p.Cin + c;
-}
 
 // ---- one 16 x 64 fp32 strip (ld 68) of a wave's accumulators -> C, through the epilogue.  Vector form: a lane owns 8 consecutive
 // columns of one row (16-byte bias / scale / residual loads, one 16-byte bf16 store or two float4 stores) whenever the row
@@ -826,7 +766,10 @@ static bool conv3_halo_plan(int mode, int amode, const GemmP& p, int* dev_out, v
 extern "C" int car_conv3_halo64_ok(int mode, const GemmP* pp) {
     return conv3_halo_plan(mode, AMODE_CONV3, *pp, nullptr, nullptr) && !CAR_KNOB("CAR_CONV_HALO128") && !CAR_KNOB("CAR_GN_UNFUSED");
 }
-// returns 0, or -1 when GemmP::gn_part is set on a call that cannot take conv3_halo64_kernel (the caller did not ask car_conv3_halo64_ok): nothing is launched
+// returns 0, or -1 when GemmP::gn_part is set on a call that cannot take conv3_halo64_kernel (the caller did not ask car_conv3_halo64_ok): nothing is launched;
+// -2 when the split kernel's launch set-up failed (GemmP::split3; the dynamic-LDS attribute): nothing is launched either
+extern "C" int car_gemm_split_ok(int amode, const GemmP* pp);                                   // gemm_split.hip
+extern "C" hipError_t car_launch_gemm_split(int amode, const GemmP* pp, hipStream_t st);
 extern "C" int car_launch_gemm(int mode, int amode, const GemmP* pp, hipStream_t st) {
     GemmP p = *pp;
     if (p.nb0 <= 0) p.nb0 = 1;
@@ -893,6 +836,8 @@ extern "C" int car_launch_gemm(int mode, int amode, const GemmP* pp, hipStream_t
     } else {
         if (p.gn_part) return -1;                 // GroupNorm partials are a bf16 conv3_halo64_kernel feature
         p.patch = 0;                              // the exact-mode kernel enumerates pixels linearly
+        // opt-in split-bf16 arithmetic (gemm_split.hip): three bf16 MFMAs per fp32 product where the one predicate holds; every other call is exact fp32 as below
+        if (p.split3 && car_gemm_split_ok(amode, &p)) return car_launch_gemm_split(amode, &p, st) == hipSuccess ? 0 : -2;
         // exact mode: fp32 MFMA tiles (16 x the VALU rate per CU); the round-1 VALU kernel serves the shapes whose strides break the loader's 16-byte chunks
         const bool mfma_ok = p.K % 16 == 0 && p.ldw % 4 == 0 && ((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.W & 15) == 0 && p.sA0 % 4 == 0 && p.sA1 % 4 == 0 && p.sW0 % 4 == 0 && p.sW1 % 4 == 0 &&
                              (amode == AMODE_PLAIN ? p.lda % 4 == 0 : p.Cin % 4 == 0);

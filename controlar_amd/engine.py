@@ -43,7 +43,7 @@ class Engine:
     """One context = one set of weights in one arithmetic mode ('fp32' exact | 'bf16' fast)."""
 
     def __init__(self, cfg: PathConfig, precision: str = "bf16", device: Optional[torch.device] = None, stream_priority: int = 0,
-                 weights_fp8: bool = False, kv_fp8: bool = False, dev: Optional[bool] = None):
+                 weights_fp8: bool = False, kv_fp8: bool = False, dev: Optional[bool] = None, vq_split: bool = False):
         # dev=True: the development build of the library (the CAR_* A/B switches exist only there; default: CONTROLAR_DEV_LIB=1 in the environment)
         self.lib = L.load(dev)
         if not torch.cuda.is_available():
@@ -56,6 +56,8 @@ class Engine:
         self.cfg = cfg
         self.precision = precision
         self.mode = {"fp32": L.CAR_F32, "none": L.CAR_F32, "bf16": L.CAR_BF16}[precision]
+        if vq_split and self.mode != L.CAR_F32:
+            raise ValueError("vq_split=True (car_config.vq_split_bf16) is an option of the fp32 mode: the bf16 mode decodes on bf16 operands already")
         self.dtype = torch.float32 if self.mode == L.CAR_F32 else torch.bfloat16
         g, v, q = cfg.gpt, cfg.vit, cfg.vq
         cc = L.CarConfig()
@@ -77,6 +79,9 @@ class Engine:
         cc.decode_weight_fp8 = 2 if weights_fp8 in ("mfma", 2) else int(bool(weights_fp8))
         # opt-in e4m3 KV cache (bf16 mode only; bf16 KV is the default and the parity path): halves the KV stream, doubles the sequences that fit
         cc.kv_cache_fp8 = int(bool(kv_fp8))
+        # opt-in split-bf16 VQ decoder (fp32 mode only): each fp32 conv / GEMM operand as two bf16 numbers, three bf16 MFMAs per product — fp32-grade pixels
+        # (the exact decoder's tolerance against the reference) at a multiple of the fp32 MFMA's rate; vq_encode, generate and encode_control are untouched
+        cc.vq_split_bf16 = int(bool(vq_split))
         cc.codebook_size, cc.codebook_dim, cc.z_channels, cc.vq_ch = q.codebook_size, q.codebook_embed_dim, q.z_channels, q.ch
         cc.vq_num_res_blocks, cc.vq_n_mult, cc.gn_eps = q.num_res_blocks, len(q.ch_mult), q.gn_eps
         for i, m in enumerate(q.ch_mult):

@@ -176,7 +176,9 @@ class VQModel:
             from .config import tiny_t2i
             cfg = tiny_t2i()                   # GPT/ViT halves of the context stay empty
             cfg.vq = self.vq
-            self._engine = Engine(cfg, "bf16" if self._dtype == torch.bfloat16 else "fp32", device=self._device)
+            # library-side opt-in modes, as on the GPT drop-in: `vq.engine_options = {"vq_split": True}` before the first decode_code selects the split-bf16
+            # decoder for an fp32 model (fp32-grade pixels at a multiple of the fp32 decoder's speed; tolerance-graded, the reference has no such arithmetic)
+            self._engine = Engine(cfg, "bf16" if self._dtype == torch.bfloat16 else "fp32", device=self._device, **getattr(self, "engine_options", {}))
             self._engine.load_state_dict(self._sd, finalize=True)
         return self._engine
 

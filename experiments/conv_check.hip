@@ -4,6 +4,7 @@
 // then isolated times at the decoder's shapes.  Test infrastructure.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I controlar_amd/csrc experiments/conv_check.hip -o experiments/conv_check && experiments/conv_check
 #include "../controlar_amd/csrc/gemm.hip"
+#include "../controlar_amd/csrc/gemm_split.hip"
 #include "../controlar_amd/csrc/ops.hip"
 
 #include <cmath>

@@ -5,6 +5,7 @@
 // before a fused-epilogue kernel is written.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I controlar_amd/csrc experiments/gemm_mid.hip -o experiments/gemm_mid && experiments/gemm_mid
 #include "../controlar_amd/csrc/gemm.hip"
+#include "../controlar_amd/csrc/gemm_split.hip"
 
 #include <cstdio>
 #include <cstdlib>

@@ -72,7 +72,14 @@ typedef struct car_config {
                                   rotated K and V are rounded to e4m3 when they are stored, widened to bf16 in registers in front of the same bf16 MFMAs; the
                                   prefill's own attention reads the unrounded rows.  Halves the dominant HBM stream of large batches and doubles the sequences
                                   that fit.  The reference has no such mode: tolerance-graded against the oracle running the same model (kv_fp8=True). */
-    int32_t reserved[2];
+    int32_t vq_split_bf16;    /* CAR_F32 only, opt-in (0 = the default: every GEMM-shaped layer of car_vq_decode on the exact fp32 MFMA).  1 = the decoder's convolutions
+                                  (3x3, 1x1) and the AttnBlock's two batched GEMMs take each fp32 operand as two bf16 numbers, hi = bf16(x) and lo = bf16(x - hi), and
+                                  a product as three bf16 MFMAs accumulating in fp32 (hi*hi + hi*lo + lo*hi; relative product error about 2^-16) wherever a layer's
+                                  K and channel count are multiples of 32; a layer that is not runs exact fp32 as with 0.  Activations, GroupNorm, softmax, the codebook
+                                  lookup and conv_out stay fp32; car_vq_encode and the transformer never use it.  Stands for the fp32 convolutions of
+                                  tokenizer/tokenizer_image/vq_model.py:53-56,129-195.  The reference has no such arithmetic: held to the exact decoder's own tolerance
+                                  against the reference's pixels, max <= 2e-3 and mean <= 1e-4 (tests/test_vq_split_gpu.py; profiles/vq_split_parity_measured.jsonl) */
+    int32_t reserved[1];
 } car_config;
 
 /* sampling parameters — reference: generate.py:59-74 sample(), :134 generate() kwargs */
@@ -353,6 +360,10 @@ int car_debug_resample_coeffs(int32_t in_size, double in0, double in1, int32_t o
 
 /* Host-only: fp32 -> OCP e4m3fn bytes with the library's rounding (round-to-nearest-even, saturating at 448). */
 int car_debug_f32_to_e4m3(const float* in, unsigned char* out, int64_t n);
+
+/* Host-only: the operand split of car_config.vq_split_bf16 on n values: hi[i] = round-to-nearest-even bf16 bits of x[i], lo[i] = RNE bf16 bits of
+ * x[i] - float(hi[i]); where hi[i] is not finite (inf, NaN, or a value that rounds to inf) lo[i] is zero. */
+int car_debug_split_bf16(const float* x, int64_t n, uint16_t* hi, uint16_t* lo);
 
 /* Copies the cached control tokens of layer-group k (0..2) [b,n_tok,dim] as fp32 to a HOST buffer (tests). */
 int car_debug_control_tokens(car_ctx* ctx, int32_t k, float* host_out, int64_t max_elems);
