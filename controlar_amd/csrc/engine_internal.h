@@ -154,6 +154,7 @@ struct car_ctx {
     ResampleAxis rs_axis[2];   // car_resize: the last table set, [0] horizontal, [1] vertical
     hipEvent_t ev_rs = nullptr;   // recorded behind the last table upload: the host copies are rewritten only after it
     DevBuf resize_ws;    // car_resize: the uint8 intermediate between the horizontal and the vertical pass (grows on demand)
+    DevBuf metrics_ws;   // car_ms_ssim / car_f1 / car_rmse: per-block partials and, for MS-SSIM, the pooled images of scales 2..5 (grows on demand)
     car_t5_config t5 = {}; bool has_t5 = false;
     DevBuf t5_in;        // int32 ids [B*T] | uint8 key mask [B*T] | staging for host-side int64 inputs
     DevBuf t5_bias; int t5_bias_T = 0;   // position bias fp32 [heads][T][T] of the last sequence length

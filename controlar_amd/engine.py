@@ -292,6 +292,108 @@ class Engine:
         extra = tuple(t for t in (ctrl, fl) if t is not None)
         return (out,) + extra if extra else out
 
+    # ------------------------------------------------------------------ control-consistency metrics (evaluations/*.py, autoregressive/test/metric.py)
+    def _metric_input(self, t: torch.Tensor, what: str) -> torch.Tensor:
+        """uint8 stays uint8, everything else becomes fp32; on the device, contiguous."""
+        if not torch.is_tensor(t):
+            raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
+        return t.to(device=self.device, dtype=torch.uint8 if t.dtype == torch.uint8 else torch.float32).contiguous()
+
+    @staticmethod
+    def _metric_dt(t: torch.Tensor) -> int:
+        return L.CAR_DT_U8 if t.dtype == torch.uint8 else L.CAR_DT_F32
+
+    def ms_ssim(self, pred: torch.Tensor, target: torch.Tensor, scale=None, want_scales: bool = False):
+        """torchmetrics' MultiScaleStructuralSimilarityIndexMeasure(data_range=1.0) per image on the GPU (car_ms_ssim).  pred, target [B,C,H,W] (or
+        [B,H,W] = one channel), each uint8 or float; an element's value is clip(v * scale, 0, 1).  scale: one number for both inputs, a pair
+        (pred, target), or None = 1/255 for a uint8 input and 1 for a float one.  Returns fp64 [B]; with want_scales also fp64 [B,5,2], per scale the
+        (ssim, cs) means after relu.  Sides below 176 raise ValueError, as torchmetrics does (side // 16 <= 10)."""
+        if pred.shape != target.shape:
+            raise ValueError(f"ms_ssim: pred and target differ in shape: {tuple(pred.shape)} and {tuple(target.shape)}")
+        if pred.dim() == 3:
+            pred, target = pred[:, None], target[:, None]
+        if pred.dim() != 4:
+            raise ValueError(f"ms_ssim: expected [B,C,H,W] or [B,H,W], got {tuple(pred.shape)}")
+        B, ch, H, W = pred.shape
+        if H < 32 or W < 32:
+            raise ValueError(f"ms_ssim: with 5 scales both sides must be at least 32, got {H} x {W}")
+        if H // 16 <= 10 or W // 16 <= 10:
+            raise ValueError(f"ms_ssim: with 5 scales and an 11 x 11 window both sides must be at least 176 (side // 16 > 10), got {H} x {W}")
+        if B == 0 or ch == 0:
+            raise ValueError(f"ms_ssim: empty batch {tuple(pred.shape)}")
+        p, t = self._metric_input(pred, "ms_ssim"), self._metric_input(target, "ms_ssim")
+        sp, st = scale if isinstance(scale, (tuple, list)) else (scale, scale)
+        sp = (1.0 / 255.0 if p.dtype == torch.uint8 else 1.0) if sp is None else float(sp)
+        st = (1.0 / 255.0 if t.dtype == torch.uint8 else 1.0) if st is None else float(st)
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        tab = torch.empty(B, 5, 2, dtype=torch.float64, device=self.device) if want_scales else None
+        self._check(self.lib.car_ms_ssim(self._h, C.c_void_p(p.data_ptr()), self._metric_dt(p), C.c_void_p(t.data_ptr()), self._metric_dt(t), B, ch, H, W,
+                                         sp, st, C.c_void_p(out.data_ptr()), C.c_void_p(tab.data_ptr() if tab is not None else 0),
+                                         C.c_void_p(_stream_ptr())), "car_ms_ssim")
+        return (out, tab) if want_scales else out
+
+    @staticmethod
+    def _f1_rule(value, threshold, what):
+        if (value is None) == (threshold is None):
+            raise ValueError(f"f1: give {what} exactly one rule, value= (positive where v == value) or threshold= (positive where v > threshold)")
+        return (0, float(value)) if value is not None else (1, float(threshold))
+
+    def f1(self, pred: torch.Tensor, target: torch.Tensor, value=None, threshold=None, target_value=None, target_threshold=None, want_counts: bool = False):
+        """Binary F1 per image on the GPU (car_f1).  pred, target [B,H,W] (or [H,W]), each uint8 or float.  An element is positive where v == value
+        (evaluations/canny_f1score.py: value=255) or where v > threshold (metric.py's F1score: threshold=128); target_value / target_threshold give the
+        target a rule of its own, otherwise it shares pred's.  Returns fp64 [B] = 2TP / (2TP + FP + FN), 0 where that denominator is 0; with want_counts
+        also int64 [B,3] = TP, FP, FN."""
+        if pred.shape != target.shape:
+            raise ValueError(f"f1: pred and target differ in shape: {tuple(pred.shape)} and {tuple(target.shape)}")
+        single = pred.dim() == 2
+        if single:
+            pred, target = pred[None], target[None]
+        if pred.dim() != 3 or pred.numel() == 0:
+            raise ValueError(f"f1: expected non-empty [B,H,W] or [H,W], got {tuple(pred.shape)}")
+        rp, vp = self._f1_rule(value, threshold, "pred")
+        rt, vt = (rp, vp) if target_value is None and target_threshold is None else self._f1_rule(target_value, target_threshold, "target")
+        p, t = self._metric_input(pred, "f1"), self._metric_input(target, "f1")
+        B, H, W = p.shape
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        cnt = torch.empty(B, 3, dtype=torch.int64, device=self.device) if want_counts else None
+        self._check(self.lib.car_f1(self._h, C.c_void_p(p.data_ptr()), self._metric_dt(p), rp, vp, C.c_void_p(t.data_ptr()), self._metric_dt(t), rt, vt,
+                                    B, H, W, C.c_void_p(cnt.data_ptr() if cnt is not None else 0), C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())),
+                    "car_f1")
+        if single:
+            out, cnt = out[0], (cnt[0] if cnt is not None else None)
+        return (out, cnt) if want_counts else out
+
+    def rmse(self, pred: torch.Tensor, label: torch.Tensor, scale_to_max: bool = False) -> torch.Tensor:
+        """sqrt(mean((pred * s - label)^2)) per image on the GPU (car_rmse).  pred float [B,H,W] (or [H,W]), label uint8 or float of the same shape.
+        s = 1, or with scale_to_max 255 / max(pred) of that image (evaluations/depth_rmse.py:59).  Returns fp64 [B]."""
+        if pred.shape != label.shape:
+            raise ValueError(f"rmse: pred and label differ in shape: {tuple(pred.shape)} and {tuple(label.shape)}")
+        single = pred.dim() == 2
+        if single:
+            pred, label = pred[None], label[None]
+        if pred.dim() != 3 or pred.numel() == 0:
+            raise ValueError(f"rmse: expected non-empty [B,H,W] or [H,W], got {tuple(pred.shape)}")
+        p, t = pred.to(device=self.device, dtype=torch.float32).contiguous(), self._metric_input(label, "rmse")
+        B, H, W = p.shape
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        self._check(self.lib.car_rmse(self._h, C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), self._metric_dt(t), B, H, W, int(bool(scale_to_max)),
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())), "car_rmse")
+        return out[0] if single else out
+
+    def pixels_to_u8(self, x: torch.Tensor, want_float: bool = False):
+        """torchvision's save_image(normalize=True, value_range=(-1, 1)) quantiser on the GPU (car_pixels_to_u8; autoregressive/test/test_t2i.py:233-234).
+        x float [B,3,H,W] in [-1,1] (values outside are clamped) -> uint8 [B,H,W,3], what canny and resize take; with want_float also fp32 [B,3,H,W]
+        holding the same 0..255 values, what hed and lineart take."""
+        if x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+            raise ValueError(f"pixels_to_u8: expected a non-empty image batch [B,3,H,W], got {tuple(x.shape)}")
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        B, _, H, W = x.shape
+        out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
+        fl = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device) if want_float else None
+        self._check(self.lib.car_pixels_to_u8(self._h, C.c_void_p(x.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(fl.data_ptr() if fl is not None else 0), C.c_void_p(_stream_ptr())), "car_pixels_to_u8")
+        return (out, fl) if want_float else out
+
     def load_lineart(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
         """LineArt().state_dict() names (condition/lineart.py:26-72: model0.1.weight ... model4.1.bias); the C ABI namespaces them under 'lineart.'."""
         self.load_state_dict({"lineart." + k: v for k, v in sd.items()}, finalize=finalize)

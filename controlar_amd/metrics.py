@@ -1,0 +1,150 @@
+"""Control consistency on the GPU: does a generated image obey the control it was given?  This is the scoring step of the reference's
+``evaluations/canny_f1score.py``, ``hed_ssim.py``, ``lineart_ssim.py`` and ``depth_rmse.py`` and the accumulators of ``autoregressive/test/metric.py``,
+without saved PNGs, torchmetrics, skimage or sklearn: ``car_ms_ssim``, ``car_f1``, ``car_rmse`` and ``car_pixels_to_u8`` behind ``Engine``.
+
+``SSIM``, ``F1score`` and ``RMSE`` keep ``metric.py``'s call shape (``update(img1, img2)`` / ``calculate()``); ``ControlConsistency`` runs a whole
+evaluation script for one batch: quantise as ``save_image`` does, re-extract the condition, score it against the control that was fed in."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .config import tiny_t2i
+from .engine import Engine
+
+CONDITION_TYPES = ("canny", "hed", "lineart", "depth")
+
+
+def _engine(engine, device=None) -> Engine:
+    return engine if engine is not None else Engine(tiny_t2i(), "bf16", device=device)      # the kernels need no weights: any context serves
+
+
+def _t(x) -> torch.Tensor:
+    return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _batched(x: torch.Tensor, lead: int) -> torch.Tensor:
+    """[H,W] -> [1, (1,) H, W]; batches pass."""
+    while x.dim() < lead:
+        x = x[None]
+    return x
+
+
+class _Accumulator:
+    """``update`` adds the batch mean and counts one, as the evaluation scripts append one value per batch; ``per_image`` keeps every value."""
+
+    def __init__(self, engine=None, device=None):
+        self._eng = _engine(engine, device)
+        self.total = torch.zeros((), dtype=torch.float64, device=self._eng.device)
+        self.count = 0
+        self._values = []
+
+    def _add(self, values: torch.Tensor) -> torch.Tensor:
+        self._values.append(values)
+        self.total = self.total + values.mean()
+        self.count += 1
+        return values
+
+    @property
+    def per_image(self) -> torch.Tensor:
+        """Every image's value so far, fp64, in the order of the updates."""
+        return torch.cat(self._values) if self._values else torch.empty(0, dtype=torch.float64, device=self._eng.device)
+
+    def calculate(self) -> float:
+        if self.count == 0:
+            raise ValueError("No images have been added.")
+        return float(self.total / self.count)
+
+
+class SSIM(_Accumulator):
+    """``metric.py``'s ``SSIM`` in call shape: raw 0..255 maps in, ``(img/255).clip(0,1)`` scored.  DEVIATION from ``metric.py``: that class builds the
+    torchmetrics MS-SSIM object, drops it, and then calls skimage's single-scale ``structural_similarity``.  This one computes multi-scale SSIM, which is
+    what every ``evaluations/*_ssim.py`` script and the paper report.  img1, img2: [H,W], [B,H,W] or [B,C,H,W], uint8 or float, sides >= 176."""
+
+    def __init__(self, data_range=1.0, engine=None, device=None):
+        super().__init__(engine, device)
+
+    def update(self, img1, img2) -> torch.Tensor:
+        a, b = _batched(_t(img1), 3), _batched(_t(img2), 3)
+        return self._add(self._eng.ms_ssim(a, b, scale=1.0 / 255.0))
+
+
+class F1score(_Accumulator):
+    """``metric.py``'s ``F1score``: both maps are binarised with ``> threshold`` (128), F1 of the positive class (sklearn's ``f1_score``; 0 where
+    neither map has a positive).  img1, img2: [H,W] or [B,H,W], uint8 or float."""
+
+    def __init__(self, threshold=128, engine=None, device=None):
+        super().__init__(engine, device)
+        self.threshold = threshold
+
+    def update(self, img1, img2) -> torch.Tensor:
+        a, b = _batched(_t(img1), 3), _batched(_t(img2), 3)
+        return self._add(self._eng.f1(b, a, threshold=self.threshold))           # metric.py: y_true from img1, y_pred from img2
+
+
+class RMSE(_Accumulator):
+    """``metric.py``'s ``RMSE``: sqrt(mean((img1 - img2)^2)) of the values as they are.  img1 float, img2 uint8 or float: [H,W] or [B,H,W]."""
+
+    def update(self, img1, img2) -> torch.Tensor:
+        a, b = _batched(_t(img1), 3), _batched(_t(img2), 3)
+        return self._add(self._eng.rmse(a, b))
+
+
+class ControlConsistency:
+    """One evaluation script per condition type, on the device.  ``__call__(pixels, control)``: ``pixels`` [B,3,H,W] in [-1,1] straight from
+    ``vq_decode``, ``control`` [B,3,H,W] in [-1,1] as it was fed to ``generate``.  Both are quantised as ``save_image(normalize=True,
+    value_range=(-1,1))`` writes them (the scripts read those PNGs back); channel 0 of the control is the label.  Then, as the script for the type does:
+
+    - ``'canny'``   ``CannyDetector`` at thresholds 100 / 200; F1 of the ``== 255`` maps                       (evaluations/canny_f1score.py)
+    - ``'hed'``     ``HEDdetector`` output / 255 and label / 255, clipped; MS-SSIM                              (evaluations/hed_ssim.py)
+    - ``'lineart'`` ``LineArt`` output as it is (0..1) and label / 255, clipped; MS-SSIM                        (evaluations/lineart_ssim.py)
+    - ``'depth'``   ``DepthEstimator.preprocess(size=depth_size)``, the model, ``d * 255 / max``; RMSE against the label, which must have that size
+                    (evaluations/depth_rmse.py; 512 x 512 there)
+
+    ``extractor``: the ``condition.CannyDetector`` / ``HEDdetector`` / ``LineArt`` / ``DepthEstimator`` the caller already holds (its weights loaded);
+    for ``'canny'`` a new one by default.  Returns ``(per_image fp64 [B], mean)``, both on the device; nothing is copied to the host."""
+
+    def __init__(self, condition_type: str, extractor=None, depth_size=(512, 512), device=None):
+        if condition_type not in CONDITION_TYPES:
+            raise ValueError(f"condition_type {condition_type!r}: one of {CONDITION_TYPES}")
+        if extractor is None:
+            if condition_type != "canny":
+                raise ValueError(f"condition_type {condition_type!r} needs the extractor that holds its weights (only 'canny' has none)")
+            from .condition import CannyDetector
+            extractor = CannyDetector(device=device)
+        self.condition_type = condition_type
+        self.extractor = extractor
+        self.depth_size = (int(depth_size[0]), int(depth_size[1]))
+        self._eng = extractor._eng             # the metric kernels need no weights: the extractor's context serves
+
+    def extract(self, pixels: torch.Tensor) -> torch.Tensor:
+        """The condition of ``pixels`` [B,3,H,W] in [-1,1], in the units the script scores: uint8 [B,H,W] edges (canny), fp32 [B,H,W] in 0..255 (hed),
+        fp32 [B,1,Ho,Wo] in 0..1 (lineart), fp32 [B,S,S] predicted depth (depth)."""
+        e, kind = self._eng, self.condition_type
+        if kind == "canny":
+            return e.canny(e.pixels_to_u8(pixels), 100, 200)
+        if kind == "hed":
+            return e.hed(e.pixels_to_u8(pixels, want_float=True)[1])
+        if kind == "lineart":
+            return e.lineart(e.pixels_to_u8(pixels, want_float=True)[1])
+        pv = self.extractor.preprocess(e.pixels_to_u8(pixels).permute(0, 3, 1, 2), size=self.depth_size)
+        return e.depth(pv)
+
+    def label(self, control: torch.Tensor) -> torch.Tensor:
+        """Channel 0 of the control image as ``save_image`` writes it: uint8 [B,H,W]."""
+        return self._eng.pixels_to_u8(control)[..., 0].contiguous()
+
+    def __call__(self, pixels: torch.Tensor, control: torch.Tensor):
+        e, kind = self._eng, self.condition_type
+        got, want = self.extract(pixels), self.label(control)
+        if tuple(got.shape[-2:]) != tuple(want.shape[-2:]):
+            raise ValueError(f"the re-extracted {kind} map is {tuple(got.shape[-2:])} and the control is {tuple(want.shape[-2:])}: the script compares them pixel by pixel")
+        if kind == "canny":
+            vals = e.f1(got, want, value=255)
+        elif kind == "hed":
+            vals = e.ms_ssim(got[:, None], want[:, None], scale=(1.0 / 255.0, 1.0 / 255.0))
+        elif kind == "lineart":
+            vals = e.ms_ssim(got, want[:, None], scale=(1.0, 1.0 / 255.0))
+        else:
+            vals = e.rmse(got, want, scale_to_max=True)
+        return vals, vals.mean()

@@ -195,6 +195,46 @@ int car_resize(car_ctx* ctx, const uint8_t* img_hwc, int32_t B, int32_t H, int32
                uint8_t* out_hwc, void* control_out, float* float_out, int32_t norm, void* stream);
 
 /*
+ * Control-consistency metrics — replace the scoring of evaluations/hed_ssim.py, lineart_ssim.py, canny_f1score.py, depth_rmse.py and the accumulators of
+ * autoregressive/test/metric.py (torchmetrics / sklearn on saved PNGs) on tensors that are already on the device.  All four entries work on any
+ * context (no weights needed), are deterministic (no atomics: per-block partials folded per image in a fixed order), batch-invariant per image, and do
+ * not synchronise with the host.  Element types are the CAR_DT_* codes; metric inputs are CAR_DT_F32 or CAR_DT_U8.  Results are fp64: every sum is
+ * accumulated in fp64 on the device.  A refused call leaves the context usable.
+ *
+ * Multi-scale SSIM — torchmetrics' MultiScaleStructuralSimilarityIndexMeasure(data_range=1.0) with its defaults (11 x 11 Gaussian window, sigma 1.5,
+ * k1 0.01, k2 0.03, betas 0.0448 0.2856 0.3001 0.2363 0.1333, relu normalisation).  pred, target: [B,C,H,W], each fp32 or uint8; the value of an
+ * element is clip(v * scale, 0, 1) with that input's scale (1 for maps in 0..1, 1/255 for raw 0..255 maps, as the scripts divide and clip).  out: fp64
+ * [B], the per-image value; scales_out: fp64 [B,5,2], per scale the means of the ssim and of the contrast-sensitivity map after relu, or NULL.  Both sides
+ * must be at least 176 (torchmetrics refuses side / 16 <= 10).  Six launches: one per scale, which stages a halo tile of both images in LDS, filters the
+ * five maps separably from there, reduces ssim and cs to one pair per tile and writes the 2 x 2-pooled images of the next scale; and one fold.
+ */
+int car_ms_ssim(car_ctx* ctx, const void* pred, int32_t pred_dtype, const void* target, int32_t target_dtype,
+                int32_t B, int32_t C, int32_t H, int32_t W, double pred_scale, double target_scale,
+                double* out, double* scales_out, void* stream);
+/*
+ * Binary F1 of two maps [B,H,W], each fp32 or uint8.  An element is positive by its map's rule: 0 = (v == value) (canny_f1score.py: == 255), 1 =
+ * (v > value) (metric.py's F1score: > 128).  counts_out: int64 [B,3] = TP, FP, FN per image (FP: pred positive, target not), or NULL; f1_out: fp64 [B] =
+ * 2 TP / (2 TP + FP + FN), 0 where the denominator is 0 (what torchmetrics and sklearn return), or NULL; not both NULL.  Integer partials: exact.
+ */
+int car_f1(car_ctx* ctx, const void* pred, int32_t pred_dtype, int32_t pred_rule, float pred_value,
+           const void* target, int32_t target_dtype, int32_t target_rule, float target_value,
+           int32_t B, int32_t H, int32_t W, int64_t* counts_out, double* f1_out, void* stream);
+/*
+ * RMSE per image: out[b] = sqrt(mean((pred * s - label)^2)), pred fp32 [B,H,W], label fp32 or uint8 [B,H,W], out fp64 [B].  scale_to_max 0: s = 1
+ * (metric.py's RMSE); 1: s = 255 / max(pred[b]) (depth_rmse.py:59), the maximum from a reduction of its own.  An image whose pred is zero everywhere
+ * gives NaN under scale_to_max, as the script does.
+ */
+int car_rmse(car_ctx* ctx, const float* pred, const void* label, int32_t label_dtype, int32_t B, int32_t H, int32_t W,
+             int32_t scale_to_max, double* out, void* stream);
+/*
+ * The pixel quantiser of torchvision's save_image(normalize=True, value_range=(-1, 1)) as the reference writes its samples
+ * (autoregressive/test/test_t2i.py:233-234): x fp32 [B,3,H,W] -> floor(clamp((clamp(x, -1, 1) + 1) / 2 * 255 + 0.5, 0, 255)), every step rounded to
+ * fp32 as torch rounds it.  out_hwc: uint8 [B,H,W,3], what car_canny and car_resize take, or NULL; float_out: fp32 [B,3,H,W] with the same values
+ * (raw 0..255), what car_hed and car_lineart take, or NULL; not both NULL.
+ */
+int car_pixels_to_u8(car_ctx* ctx, const float* x_nchw, int32_t B, int32_t H, int32_t W, uint8_t* out_hwc, float* float_out, void* stream);
+
+/*
  * LineArt control extraction — replaces LineArt.forward (condition/lineart.py:26-86, default constructor: 3 residual blocks, sigmoid; callers
  * sample_t2i.py:110-113,129-132, sample_t2i_MR.py, autoregressive/test/test_t2i.py:177).  img_nchw: fp32 [B,3,H,W] (device), raw 0..255 values as the
  * reference receives them.  out: fp32 [B,1,Ho,Wo] in (0,1) or NULL; control_out: [B,3,Ho,Wo] in the context's element type, = 1 - 2*out replicated over
