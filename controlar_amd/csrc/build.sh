@@ -17,7 +17,7 @@ pids=()
 for variant in rel dev; do
   if [ $variant = rel ]; then O=_obj; X=""; else O=_obj_dev; X="-DCAR_DEV_KNOBS"; fi
   for f in $SRCS; do
-    if [ ! -f $O/$f.o ] || [ $f.hip -nt $O/$f.o ] || [ car_common.h -nt $O/$f.o ] || [ decode2_params.h -nt $O/$f.o ] || [ kernel_params.h -nt $O/$f.o ] || [ decode_f32_params.h -nt $O/$f.o ] || { [ "${f#engine}" != "$f" ] && [ engine_internal.h -nt $O/$f.o ]; } || { [ $f = engine_resize ] && [ resample_tab.h -nt $O/$f.o ]; } || { { [ $f = metrics ] || [ $f = engine_metrics ]; } && [ metrics_params.h -nt $O/$f.o ]; } || { { [ $f = hed ] || [ $f = dpt ] || [ $f = lineart ]; } && [ conv_tile.h -nt $O/$f.o ]; } || { { [ $f = gemm ] || [ $f = gemm_split ]; } && [ gemm_gather.h -nt $O/$f.o ]; } || { [ $f = engine ] && [ _obj/build_id.h -nt $O/$f.o ]; } || [ ../../include/controlar_hip.h -nt $O/$f.o ]; then
+    if [ ! -f $O/$f.o ] || [ $f.hip -nt $O/$f.o ] || [ car_common.h -nt $O/$f.o ] || [ decode2_params.h -nt $O/$f.o ] || [ kernel_params.h -nt $O/$f.o ] || [ decode_f32_params.h -nt $O/$f.o ] || { [ "${f#engine}" != "$f" ] && { [ engine_internal.h -nt $O/$f.o ] || [ weight_pack.h -nt $O/$f.o ]; }; } || { [ $f = engine_resize ] && [ resample_tab.h -nt $O/$f.o ]; } || { { [ $f = metrics ] || [ $f = engine_metrics ]; } && [ metrics_params.h -nt $O/$f.o ]; } || { { [ $f = hed ] || [ $f = dpt ] || [ $f = lineart ]; } && [ conv_tile.h -nt $O/$f.o ]; } || { { [ $f = gemm ] || [ $f = gemm_split ]; } && [ gemm_gather.h -nt $O/$f.o ]; } || { [ $f = engine ] && [ _obj/build_id.h -nt $O/$f.o ]; } || [ ../../include/controlar_hip.h -nt $O/$f.o ]; then
       $HIPCC $FLAGS $X -I_obj -c $f.hip -o $O/$f.o &
       pids+=($!)
     fi

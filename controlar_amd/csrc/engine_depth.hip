@@ -1,6 +1,6 @@
 // engine_depth.hip — car_depth_configure / car_depth: the DPT depth estimator (transformers modeling_dpt.py DPTForDepthEstimation; callers
 // sample_t2i.py:33,114-116,133-139, demo/model.py:192-284).  The ViT backbone runs on the launchers car_encode_control uses (a second layer loop: the
-// first one keeps its bits untouched); the neck and the head run on dpt.hip.  Weight images: engine_weights.hip ("depth.*").
+// first one keeps its bits untouched); the neck and the head run on dpt.hip.  The loader of the weight images ("depth.*") is here too.
 // (one of the translation units behind include/controlar_hip.h; shared declarations: engine_internal.h)
 #include "engine_internal.h"
 
@@ -36,8 +36,9 @@ extern "C" int car_depth_configure(car_ctx* c, const car_dpt_config* d) {
     return 0;
 }
 
-std::vector<std::string> depth_tensor_names(const car_dpt_config& d) {
-    std::vector<std::string> v;
+// every tensor the configured DPT needs, under its "depth." name
+void depth_tensor_names(const car_ctx* c, std::vector<std::string>& v) {
+    const car_dpt_config& d = c->dpt;
     const std::string e = "depth.dpt.embeddings.";
     for (const char* s : {"cls_token", "position_embeddings", "patch_embeddings.projection.weight", "patch_embeddings.projection.bias"}) v.push_back(e + s);
     for (int l = 0; l < d.layers; ++l) {
@@ -59,7 +60,76 @@ std::vector<std::string> depth_tensor_names(const car_dpt_config& d) {
             for (const char* s : {".weight", ".bias"}) v.push_back(f + m + s);
     }
     for (const char* m : {"0", "2", "4"}) for (const char* s : {".weight", ".bias"}) v.push_back(std::string("depth.head.head.") + m + s);
-    return v;
+}
+
+// Linear weights, LayerNorm parameters and every bias a car_launch_gemm epilogue adds stay [N, K] / [N] in the context's element type; 1x1 convs drop their
+// trailing 1x1; 3x3 conv weights become implicit-GEMM images [Cout][9*Cin] (k = tap*Cin + ci); a ConvTranspose2d(k = stride) weight [Cin, Cout, k, k] becomes
+// the GEMM image [(ky*k + kx)*Cout + co][ci] and its bias is replicated per tap; the biases dpt_conv adds in its fp32 epilogue stay fp32; position_embeddings
+// stays on the host (resized per grid).
+int depth_load_tensor(car_ctx* c, const LoadedTensor& t) {
+    const std::string& name = t.name; const char* cname = t.cname;
+    const std::vector<int64_t>& shp = t.shape; const std::vector<float>& h = t.h;
+    if (!c->has_dpt) FAIL(c, "%s: call car_depth_configure before loading depth.* tensors", cname);
+    if (starts_with(name, "depth.dpt.layernorm.") || starts_with(name, "depth.dpt.pooler.")) return 0;     // never reach the depth map
+    const car_dpt_config& d = c->dpt;
+    std::vector<std::string> names;
+    depth_tensor_names(c, names);
+    if (!has_name(names, name)) FAIL(c, "%s: not a tensor of the configured DPT depth estimator (DPTForDepthEstimation)", cname);
+    const std::string key = name.substr(6);
+    const int64_t D = d.hidden, Fh = d.fusion_hidden, G = d.pos_grid;
+    auto is_shape = [&](std::initializer_list<int64_t> ex) { return shp.size() == ex.size() && std::equal(ex.begin(), ex.end(), shp.begin()); };
+    auto conv3 = [&](int64_t Co, int64_t Ci) -> int {
+        if (!is_shape({Co, Ci, 3, 3})) FAIL(c, "%s: expected [%lld,%lld,3,3]", cname, (long long)Co, (long long)Ci);
+        return upload(c, name, pack_conv(h.data(), (int)Co, (int)Ci, 3, 3, (int)(9 * Ci)), {Co, 9 * Ci});
+    };
+    auto vec = [&](int64_t N, bool f32) -> int { if (!is_shape({N})) FAIL(c, "%s: expected [%lld]", cname, (long long)N); return upload(c, name, h, shp, f32); };
+    auto mat = [&](int64_t N, int64_t K) -> int {          // Linear [N,K] or 1x1 conv [N,K,1,1]
+        if (!is_shape({N, K}) && !is_shape({N, K, 1, 1})) FAIL(c, "%s: expected [%lld,%lld]", cname, (long long)N, (long long)K);
+        return upload(c, name, h, {N, K});
+    };
+    const bool isw = ends_with(name, ".weight");
+    int i = -1;
+    if (key == "dpt.embeddings.cls_token") { if (t.n != D) FAIL(c, "%s: expected [1,1,%lld]", cname, (long long)D); return upload(c, name, h, {D}); }
+    if (key == "dpt.embeddings.position_embeddings") {
+        if (t.n != (G * G + 1) * D) FAIL(c, "%s: expected [1,%lld,%lld]", cname, (long long)(G * G + 1), (long long)D);
+        for (auto& kv : c->depth_pos_cache) (void)hipFree(kv.second);
+        c->depth_pos_cache.clear(); c->host_keep[name] = h; return 0;
+    }
+    if (key == "dpt.embeddings.patch_embeddings.projection.weight") { if (!is_shape({D, 3, 16, 16})) FAIL(c, "%s: expected [%lld,3,16,16]", cname, (long long)D); return upload(c, name, h, {D, 768}); }
+    if (key == "dpt.embeddings.patch_embeddings.projection.bias") return vec(D, false);
+    if (starts_with(key, "dpt.encoder.layer.")) {
+        if (ends_with(key, "intermediate.dense.weight")) return mat(d.mlp, D);
+        if (ends_with(key, "intermediate.dense.bias")) return vec(d.mlp, false);
+        if (ends_with(key, "attention.output.dense.weight")) return mat(D, D);
+        if (ends_with(key, "output.dense.weight")) return mat(D, d.mlp);
+        if (isw && key.find("layernorm_") == std::string::npos) return mat(D, D);
+        return vec(D, false);
+    }
+    if (sscanf(key.c_str(), "neck.reassemble_stage.readout_projects.%d.", &i) == 1) return isw ? mat(D, 2 * D) : vec(D, false);
+    if (sscanf(key.c_str(), "neck.reassemble_stage.layers.%d.", &i) == 1) {
+        const int64_t Ci = d.neck_hidden[i];
+        if (key.find(".projection.") != std::string::npos) return isw ? mat(Ci, D) : vec(Ci, false);
+        if (i == 3) return isw ? conv3(Ci, Ci) : vec(Ci, true);
+        const int k = i == 0 ? 4 : 2;
+        if (!isw) {
+            if (!is_shape({Ci})) FAIL(c, "%s: expected [%lld]", cname, (long long)Ci);
+            return upload(c, name, pack_convT_taps_bias(h.data(), (int)Ci, k), {(int64_t)k * k * Ci});
+        }
+        if (!is_shape({Ci, Ci, k, k})) FAIL(c, "%s: expected [%lld,%lld,%d,%d]", cname, (long long)Ci, (long long)Ci, k, k);
+        return upload(c, name, pack_convT_taps(h.data(), (int)Ci, (int)Ci, k), {(int64_t)k * k * Ci, Ci});
+    }
+    if (sscanf(key.c_str(), "neck.convs.%d.", &i) == 1) return conv3(Fh, d.neck_hidden[i]);
+    if (starts_with(key, "neck.fusion_stage.layers.")) {
+        if (key.find(".projection.") != std::string::npos) return isw ? mat(Fh, Fh) : vec(Fh, false);
+        return isw ? conv3(Fh, Fh) : vec(Fh, true);
+    }
+    if (key == "head.head.0.weight") return conv3(Fh / 2, Fh);
+    if (key == "head.head.0.bias") return vec(Fh / 2, true);
+    if (key == "head.head.2.weight") return conv3(32, Fh / 2);
+    if (key == "head.head.2.bias") return vec(32, true);
+    if (key == "head.head.4.weight") { if (!is_shape({1, 32, 1, 1})) FAIL(c, "%s: expected [1,32,1,1]", cname); return upload(c, name, h, {32}); }
+    if (key == "head.head.4.bias") return vec(1, true);
+    FAIL(c, "%s: not a tensor of the configured DPT depth estimator", cname);
 }
 
 // DPTViTEmbeddings._resize_pos_embed: the grid part through F.interpolate(mode="bilinear") (align_corners = False, no antialiasing), the CLS row untouched;

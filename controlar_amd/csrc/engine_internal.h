@@ -20,6 +20,7 @@
 #include "decode2_params.h"
 #include "decode_f32_params.h"
 #include "kernel_params.h"
+#include "weight_pack.h"
 extern "C" {
 int car_launch_dec_gemm_cfg(const GemmDP* p, int epi, int cfg, hipStream_t st);
 int car_launch_dec_gemm_cfg_ex(const GemmDP* p, int epi, int cfg, int staged_ok, hipStream_t st);
@@ -188,7 +189,7 @@ static inline size_t rup(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline bool ends_with(const std::string& s, const char* suf) { size_t n = strlen(suf); return s.size() >= n && s.compare(s.size() - n, n, suf) == 0; }
 static inline bool starts_with(const std::string& s, const char* pre) { return s.compare(0, strlen(pre), pre) == 0; }
 
-static inline const void* Wp(car_ctx* c, const std::string& name) {
+static inline const void* Wp(const car_ctx* c, const std::string& name) {
     auto it = c->w.find(name);
     return it == c->w.end() ? nullptr : it->second.p;
 }
@@ -261,8 +262,35 @@ static inline void mlp_tanh(car_ctx* c, const void* x, long lda, long sA, int nb
 static inline void fence_in(car_ctx* c, hipStream_t caller) { (void)hipEventRecord(c->ev_in, caller); (void)hipStreamWaitEvent(c->stream, c->ev_in, 0); }
 static inline void fence_out(car_ctx* c, hipStream_t caller) { (void)hipEventRecord(c->ev_out, c->stream); (void)hipStreamWaitEvent(caller, c->ev_out, 0); }
 
-// engine_depth.hip: every tensor a configured DPT needs, under its "depth." name (car_finalize_weights, car_load_tensor)
-std::vector<std::string> depth_tensor_names(const car_dpt_config& d);
+// ------------------------------------------------------------------------------------- weight loading
+// One tensor on its way through car_load_tensor: the canonical name, the caller's name (messages), the shape and the values as host fp32.  `h` is the
+// dispatcher's buffer: a loader may edit it in place or move it away.
+struct LoadedTensor {
+    const std::string& name; const char* cname; const std::vector<int64_t>& shape; int64_t n; std::vector<float>& h;
+    int ndim() const { return (int)shape.size(); }
+};
+// Every model family keeps its loader and the list of tensors car_finalize_weights asks for next to its runner: engine_lineart.hip ("lineart."),
+// engine_hed.hip ("hed."), engine_depth.hip ("depth."), engine_t5.hip ("t5."), engine_vq.hip (decoder. / encoder. / quant* / post_quant_conv.),
+// engine_weights.hip (the GPT and its ViT adapter).  A name list holds what the loaders leave in car_ctx::w (host_keep for the DPT position table).
+int lineart_load_tensor(car_ctx* c, const LoadedTensor& t);
+int hed_load_tensor(car_ctx* c, const LoadedTensor& t);
+int depth_load_tensor(car_ctx* c, const LoadedTensor& t);
+int t5_load_tensor(car_ctx* c, const LoadedTensor& t);
+int vq_load_tensor(car_ctx* c, const LoadedTensor& t);
+int gpt_load_tensor(car_ctx* c, const LoadedTensor& t);
+void lineart_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+void hed_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+void depth_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+void t5_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+void vq_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+void gpt_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+// engine_weights.hip
+int upload(car_ctx* c, const std::string& name, const std::vector<float>& h, const std::vector<int64_t>& shape, bool force_f32 = false);   // host fp32 -> c->w[name] in the element type (or fp32)
+int ensure_w(car_ctx* c, const std::string& name, size_t bytes, const std::vector<int64_t>& shape, int64_t numel);
+// one half [rows, cols] of a gated feed-forward pair (names ending in sfx_a / sfx_b, of equal length): the first to arrive waits in host_keep, the second
+// uploads the 16-row interleaved image under the name ending in sfx_joint and releases the first
+int load_interleaved_half(car_ctx* c, const LoadedTensor& t, const char* sfx_a, const char* sfx_b, const char* sfx_joint, int rows, int cols);
+static inline bool has_name(const std::vector<std::string>& names, const std::string& name) { return std::find(names.begin(), names.end(), name) != names.end(); }
 
 // engine_encode.hip
 int get_resize(car_ctx* c, int H, int W, int nh, int nw, car_ctx::ResizeTab* out);

@@ -1,5 +1,5 @@
 // engine_lineart.hip — car_lineart: the LineArt control extractor (condition/lineart.py:26-86; callers sample_t2i.py:110-113,129-132,
-// sample_t2i_MR.py, autoregressive/test/test_t2i.py:177) as a chain of lineart.hip launches.  Weight images: engine_weights.hip ("lineart.*").
+// sample_t2i_MR.py, autoregressive/test/test_t2i.py:177) as a chain of lineart.hip launches, and the loader of its weight images ("lineart.*").
 // (one of the translation units behind include/controlar_hip.h; shared declarations: engine_internal.h)
 #include "engine_internal.h"
 
@@ -13,6 +13,42 @@ int car_launch_la_out7(int mode, const void* in, const void* w, const float* bia
 }
 
 #define LACHK(ctx, x) do { const int _e = (x); if (_e != 0) FAIL(ctx, "car_lineart: %s failed: %s (%s:%d)", #x, hipGetErrorString((hipError_t)_e), __FILE__, __LINE__); } while (0)
+
+// the 24 tensors of LineArt(n_residual_blocks = 3).state_dict(), under the "lineart." prefix of the C ABI
+void lineart_tensor_names(const car_ctx*, std::vector<std::string>& v) {
+    std::vector<std::string> mods = {"model0.1", "model1.0", "model1.3"};
+    for (int r = 0; r < 3; ++r) for (const char* s : {".conv_block.1", ".conv_block.5"}) mods.push_back("model2." + std::to_string(r) + s);
+    for (const char* s : {"model3.0", "model3.3", "model4.1"}) mods.push_back(s);
+    for (auto& m : mods) { v.push_back("lineart." + m + ".weight"); v.push_back("lineart." + m + ".bias"); }
+}
+
+// Conv weights become implicit-GEMM images [Cout][taps*Cin] (k = tap*Cin + ci, K padded to the 32-wide k step) in the context's element type; a
+// ConvTranspose2d weight [Cin,Cout,3,3] becomes its four output-parity phase images (weight_pack.h pack_convT_phases).  Biases stay fp32 (only model4's is
+// applied: a bias in front of an InstanceNorm cancels).
+int lineart_load_tensor(car_ctx* c, const LoadedTensor& t) {
+    const std::string key = t.name.substr(8);
+    const std::vector<int64_t>& shp = t.shape;
+    std::vector<std::string> names;
+    lineart_tensor_names(c, names);
+    if (!has_name(names, t.name)) FAIL(c, "%s: not a tensor of the LineArt generator (n_residual_blocks = 3)", t.cname);
+    if (ends_with(t.name, ".bias")) {
+        if (t.ndim() != 1) FAIL(c, "%s: unexpected shape", t.cname);
+        return upload(c, t.name, t.h, shp, true);
+    }
+    if (t.ndim() != 4 || shp[2] != shp[3]) FAIL(c, "%s: unexpected shape", t.cname);
+    const int ks = (int)shp[2];
+    if (starts_with(key, "model3.")) {
+        const int Ci = (int)shp[0], Co = (int)shp[1];
+        if (ks != 3 || (key == "model3.0.weight" ? (Ci != 256 || Co != 128) : (Ci != 128 || Co != 64))) FAIL(c, "%s: unexpected shape", t.cname);
+        return upload(c, t.name, pack_convT_phases(t.h.data(), Ci, Co), {9, Co, Ci});
+    }
+    const int Co = (int)shp[0], Ci = (int)shp[1], Kp = conv_kp(ks * ks * Ci);
+    int eCo = 256, eCi = 256, eks = 3;
+    if (key == "model0.1.weight") { eCo = 64; eCi = 3; eks = 7; } else if (key == "model1.0.weight") { eCo = 128; eCi = 64; }
+    else if (key == "model1.3.weight") { eCo = 256; eCi = 128; } else if (key == "model4.1.weight") { eCo = 1; eCi = 64; eks = 7; }
+    if (Co != eCo || Ci != eCi || ks != eks) FAIL(c, "%s: expected [%d,%d,%d,%d]", t.cname, eCo, eCi, eks, eks);
+    return upload(c, t.name, pack_conv(t.h.data(), Co, Ci, ks, ks, Kp), {Co, Kp});
+}
 
 namespace {
 struct LaWs {                       // one chunk of images; every buffer is [nimg][per-image stride]
@@ -32,7 +68,7 @@ int conv_in_block(car_ctx* c, const LaWs& ws, int nimg, const void* in, long in_
     int Ho = Hi, Wo = Wi, tiles_img = 0;
     if (kind != 3) {
         const int ks = kind == 0 ? 7 : 3, pad = ks / 2;
-        p.ntaps = ks * ks; p.K = p.ntaps * Cin; p.Kp = (int)rup((size_t)p.K, 32); p.reflect = kind != 1;
+        p.ntaps = ks * ks; p.K = p.ntaps * Cin; p.Kp = conv_kp(p.K); p.reflect = kind != 1;
         for (int t = 0; t < p.ntaps; ++t) { p.dy[t] = (signed char)(t / ks - pad); p.dx[t] = (signed char)(t % ks - pad); }
         if (kind == 1) { p.stride = 2; Ho = (Hi - 1) / 2 + 1; Wo = (Wi - 1) / 2 + 1; }
         p.Hg = Ho; p.Wg = Wo; p.Hout = Ho; p.Wout = Wo; p.w = wp;
@@ -40,8 +76,8 @@ int conv_in_block(car_ctx* c, const LaWs& ws, int nimg, const void* in, long in_
         if (tiles_img > ws.tiles_max) FAIL(c, "car_lineart: internal error (partial slots)");
         LACHK(c, car_launch_la_conv(c->mode, &p, nimg, st));
     } else {
-        // ConvTranspose2d(k=3, s=2, p=1, output_padding=1): output (2g + py, 2g' + px).  Even parity: tap k=1 at input g; odd parity: k=2 at g and k=0 at g+1
-        // (zero beyond the edge).  1, 2, 2 and 4 taps: a quarter of the matrix work of convolving the zero-stuffed image.
+        // ConvTranspose2d(k=3, s=2, p=1, output_padding=1) as its four output-parity phases (weight_pack.h convT_phase_taps: 1, 2, 2 and 4 taps): a quarter
+        // of the matrix work of convolving the zero-stuffed image.
         Ho = 2 * Hi; Wo = 2 * Wi;
         p.Hg = Hi; p.Wg = Wi; p.Hout = Ho; p.Wout = Wo; p.os = 2; p.reflect = 0;
         const int tp = (Hi * Wi + 63) / 64;
@@ -50,9 +86,7 @@ int conv_in_block(car_ctx* c, const LaWs& ws, int nimg, const void* in, long in_
         size_t woff = 0;
         for (int ph = 0; ph < 4; ++ph) {
             p.py = ph >> 1; p.px = ph & 1;
-            const int ny = p.py ? 2 : 1, nx = p.px ? 2 : 1;
-            p.ntaps = ny * nx; p.K = p.Kp = p.ntaps * Cin;
-            for (int a = 0; a < ny; ++a) for (int b = 0; b < nx; ++b) { p.dy[a * nx + b] = (signed char)a; p.dx[a * nx + b] = (signed char)b; }
+            p.ntaps = convT_phase_taps(ph, p.dy, p.dx); p.K = p.Kp = p.ntaps * Cin;
             p.w = wp + woff * c->esz; p.tile0 = ph * tp;
             LACHK(c, car_launch_la_conv(c->mode, &p, nimg, st));
             woff += (size_t)N * p.Kp;

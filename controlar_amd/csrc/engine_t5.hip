@@ -16,6 +16,45 @@ extern "C" int car_t5_configure(car_ctx* c, const car_t5_config* t) {
     return 0;
 }
 
+// the device tensors of a loaded encoder besides t5.shared.weight, whose presence asks for them (the relative bias table of block 0 lives in host_keep)
+void t5_tensor_names(const car_ctx* c, std::vector<std::string>& v) {
+    v.push_back("t5.encoder.final_layer_norm.weight");
+    for (int i = 0; i < c->t5.num_layers; ++i) {
+        const std::string p = "t5.encoder.block." + std::to_string(i) + ".layer.";
+        for (const char* s : {"0.SelfAttention.q.weight", "0.SelfAttention.k.weight", "0.SelfAttention.v.weight", "0.SelfAttention.o.weight", "0.layer_norm.weight",
+                              "1.DenseReluDense.wi.weight", "1.DenseReluDense.wo.weight", "1.layer_norm.weight"}) v.push_back(p + s);
+    }
+}
+
+// A full T5 state dict may be offered: the decoder half, lm_head and the tied alias are skipped.
+int t5_load_tensor(car_ctx* c, const LoadedTensor& ld) {
+    const std::string& name = ld.name; const char* cname = ld.cname;
+    const std::vector<int64_t>& shp = ld.shape; const int ndim = ld.ndim();
+    if (!c->has_t5) FAIL(c, "%s: call car_t5_configure before loading t5.* tensors", cname);
+    if (starts_with(name, "t5.decoder.") || starts_with(name, "t5.lm_head.") || name == "t5.encoder.embed_tokens.weight") return 0;
+    const car_t5_config& t = c->t5;
+    if (ends_with(name, "SelfAttention.relative_attention_bias.weight")) {
+        if (ndim != 2 || shp[0] != t.rel_buckets || shp[1] != t.num_heads) FAIL(c, "%s: expected [%d,%d]", cname, t.rel_buckets, t.num_heads);
+        if (c->mode == CAR_BF16) for (auto& v : ld.h) v = bf2f(f2bf(v));          // nn.Embedding weight in the model dtype
+        c->host_keep[name] = ld.h; c->t5_bias_T = 0; return 0;
+    }
+    if (ends_with(name, "DenseReluDense.wi_0.weight") || ends_with(name, "DenseReluDense.wi_1.weight")) {
+        // wi_0 | wi_1 interleaved in blocks of 16 rows: the gated epilogue sees (gate, value) pairs (same image as w1 | w3)
+        if (ndim != 2 || shp[0] != t.d_ff || shp[1] != t.d_model) FAIL(c, "%s: expected [%d,%d]", cname, t.d_ff, t.d_model);
+        return load_interleaved_half(c, ld, "wi_0.weight", "wi_1.weight", "wi.weight", t.d_ff, t.d_model);
+    }
+    const int inner = t.num_heads * t.d_kv;
+    int64_t e0 = -1, e1 = -1;
+    if (name == "t5.shared.weight") { e0 = t.vocab_size; e1 = t.d_model; }
+    else if (ends_with(name, "SelfAttention.q.weight") || ends_with(name, "SelfAttention.k.weight") || ends_with(name, "SelfAttention.v.weight")) { e0 = inner; e1 = t.d_model; }
+    else if (ends_with(name, "SelfAttention.o.weight")) { e0 = t.d_model; e1 = inner; }
+    else if (ends_with(name, "DenseReluDense.wo.weight")) { e0 = t.d_model; e1 = t.d_ff; }
+    else if (ends_with(name, "layer_norm.weight")) { e0 = t.d_model; }
+    else FAIL(c, "%s: not a tensor of the T5 encoder (gated-gelu family)", cname);
+    if (shp.empty() || shp[0] != e0 || (e1 >= 0 && (ndim != 2 || shp[1] != e1)) || (e1 < 0 && ndim != 1)) FAIL(c, "%s: unexpected shape", cname);
+    return upload(c, name, ld.h, shp);
+}
+
 // T5Attention._relative_position_bucket, bidirectional (modeling_t5.py): rel = key - query
 static int t5_bucket(int rel, int nb, int max_distance) {
     int b = 0; const int n = nb / 2;

@@ -2,6 +2,46 @@
 // (one of the translation units behind include/controlar_hip.h; shared declarations: engine_internal.h)
 #include "engine_internal.h"
 
+// ------------------------------------------------------------------------------------- VQ weights
+// the tensors of one block of vq_layout / vq_enc_layout
+static void vq_block_names(const VqItem& it, std::vector<std::string>& v) {
+    if (it.kind == 0) {
+        for (const char* s : {".norm1.weight", ".norm1.bias", ".conv1.weight", ".conv1.bias", ".norm2.weight", ".norm2.bias", ".conv2.weight", ".conv2.bias"}) v.push_back(it.name + s);
+        if (it.cin != it.cout) { v.push_back(it.name + ".nin_shortcut.weight"); v.push_back(it.name + ".nin_shortcut.bias"); }
+    } else if (it.kind == 1) {
+        for (const char* s : {".norm.weight", ".norm.bias", ".q.weight", ".q.bias", ".k.weight", ".k.bias", ".v.weight", ".v.bias", ".proj_out.weight", ".proj_out.bias"}) v.push_back(it.name + s);
+    } else { v.push_back(it.name + ".conv.weight"); v.push_back(it.name + ".conv.bias"); }
+}
+// what a context that holds quantize.embedding.weight needs besides: the decoder, and the encode side once encoder.conv_in.weight has arrived
+void vq_tensor_names(const car_ctx* c, std::vector<std::string>& v) {
+    int last = 0;
+    for (const char* s : {"post_quant_conv.weight", "post_quant_conv.bias", "decoder.conv_in.weight", "decoder.conv_in.bias", "decoder.norm_out.weight",
+                          "decoder.norm_out.bias", "decoder.conv_out.weight", "decoder.conv_out.bias"}) v.push_back(s);
+    for (auto& it : vq_layout(c->cfg, &last)) vq_block_names(it, v);
+    if (!Wp(c, "encoder.conv_in.weight")) return;
+    for (const char* s : {"encoder.conv_in.bias", "encoder.norm_out.weight", "encoder.norm_out.bias", "encoder.conv_out.weight", "encoder.conv_out.bias",
+                          "quant_conv.weight", "quant_conv.bias"}) v.push_back(s);
+    for (auto& it : vq_enc_layout(c->cfg, &last)) vq_block_names(it, v);
+}
+
+int vq_load_tensor(car_ctx* c, const LoadedTensor& t) {
+    const std::string& name = t.name;
+    const std::vector<int64_t>& shp = t.shape;
+    if (name == "quantize.embedding.weight" || starts_with(name, "post_quant_conv.") || name == "decoder.conv_out.bias") return upload(c, name, t.h, shp, true);
+    if (name == "decoder.conv_out.weight") {      // [3,C,3,3] -> [3][9][C]
+        const int C = (int)shp[1];
+        return upload(c, name, pack_conv(t.h.data(), 3, C, 3, 3, 9 * C), {3, 9, C});
+    }
+    if (name == "encoder.conv_in.weight") return upload(c, name, t.h, {shp[0], 27});     // [Co,3,3,3] is already (ci, ky, kx)-major
+    const bool coder = starts_with(name, "decoder.") || starts_with(name, "encoder.");
+    if (coder && t.ndim() == 4 && shp[2] == 3) {      // conv3x3 [Co,Ci,3,3] -> implicit-GEMM weight [Co, 9*Ci], k = tap*Ci + ci
+        const int Co = (int)shp[0], Ci = (int)shp[1];
+        return upload(c, name, pack_conv(t.h.data(), Co, Ci, 3, 3, 9 * Ci), {Co, 9 * (int64_t)Ci});
+    }
+    if ((coder || starts_with(name, "quant_conv.")) && t.ndim() == 4) return upload(c, name, t.h, {shp[0], shp[1]});   // 1x1 conv
+    return upload(c, name, t.h, shp);
+}
+
 // ------------------------------------------------------------------------------------- VQ building blocks (shared by decode and encode)
 struct VqOps {
     car_ctx* c; int mode; size_t e; hipStream_t st;
