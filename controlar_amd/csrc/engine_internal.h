@@ -1,6 +1,6 @@
 // engine_internal.h — what the translation units of the host side share (engine.hip: lifecycle / stats / standalone sampler; engine_weights.hip: weight
 // packing, finalize, the packed-image cache; engine_encode.hip: resize tables, the control encoder, Canny; engine_generate.hip: prefill, the decode step,
-// generate; engine_t5.hip: the caption encoder; engine_vq.hip: VQ encode / decode).  Round 4 cut the single 1900-line engine.hip along its stage banners:
+// generate; engine_t5.hip: the caption encoder; engine_vq.hip: VQ encode / decode; engine_score.hip: car_score).  Round 4 cut the single 1900-line engine.hip along its stage banners:
 // no behaviour change.  Everything here is internal: the C ABI is include/controlar_hip.h.
 #pragma once
 #include "car_common.h"
@@ -144,7 +144,7 @@ struct car_ctx {
     int n_cu = 256;       // compute units of the device (persistent-grid sizing)
     DevBuf rowimg;       // [b] int: image index of each row
     DevBuf rowunc; std::vector<int> h_rowunc;   // c2i: uncond-row marks (device + the host copy the async upload reads)
-    int* host_flags = nullptr;   // sticky error flags raised by device code, in host-mapped pinned memory ([0] = class label out of range, [1] = first_valid_hint too large): the kernel writes it
+    int* host_flags = nullptr;   // sticky error flags raised by device code, in host-mapped pinned memory ([0] = class label out of range, [1] = first_valid_hint too large, [2] = car_score token id out of range): the kernel writes it
                                  // with a system-scope store, and every entry that takes this context reads it without a host wait (check_sticky)
     DevBuf canny_map;    // car_canny: uint8 [B,H,W] candidate/edge map + the "changed" flag
     DevBuf lineart_ws;   // car_lineart: NHWC activations, raw fp32 conv outputs and InstanceNorm partials of one chunk of images (grows on demand)
@@ -177,6 +177,7 @@ static inline int check_sticky(car_ctx* c) {
     if (!c->host_flags) return 0;
     volatile int* f = c->host_flags;
     if (f[1]) { f[1] = 0; FAIL(c, "car_generate: an earlier call passed a first_valid_hint beyond the first valid prompt position of its batch: valid prompt rows were left out of the prefill, its tokens are invalid"); }
+    if (f[2]) { f[2] = 0; FAIL(c, "car_score: an earlier call on this context received a token id outside [0, %d) (read as token 0 on the device): its results are invalid", c->cfg.vocab_size); }
     if (f[0]) { f[0] = 0; FAIL(c, "car_generate_c2i: an earlier call on this context received a class label outside [0, %d] (clamped to the null class on the device): its tokens are invalid", c->cfg.num_classes); }
     return 0;
 }

@@ -1,0 +1,216 @@
+// engine_score.hip — car_score: the per-token negative log-likelihood of GIVEN image tokens in one parallel pass (the training branch of
+// Transformer.forward, gpt_t2i.py:420-431,456-459,472-481, evaluated with generate()'s inference conventions), and car_debug_score_rows.
+// (one of the translation units behind include/controlar_hip.h; shared declarations: engine_internal.h)
+//
+// The causal structure makes the logits of all n_new positions computable from ONE pass over Ts = Tv + n_new - 1 rows per sequence: the Tv rows of the
+// prefix window (as car_generate's prefill, engine_generate.hip stage E) followed by the embeddings of tokens[:, :n_new-1]; the logits row that generate()
+// hands to sample() at step i is the output of sequence row Tv - 1 + i.  Stages C (control tokens) and D (text prefix) and the layer loop are the prefill's,
+// on the same generic GEMMs (row-count agnostic; every output element sums its k-blocks in order whatever M), with three differences: the control token j is
+// added on row Tv - 1 + j at layers 0, n/3, 2n/3 (rmsnorm add_mode 3; the unconditional half adds exact zeros), RoPE runs in place without a KV cache
+// (score.hip), and the final norm feeds the fused projection + cross-entropy kernel instead of a logits GEMM.  Nothing of the context that car_generate
+// reads later is changed except scratch that it rewrites itself.
+//
+// Chunk rule (fixed): at most cap = max(1, 16384 / (mult * Ts)) consecutive images per chunk (mult = 2 under CFG: an image and its unconditional twin are
+// always in the same chunk, rows [cond | uncond]); in the fp32 mode the cap is lowered until the chunk's score tensor b * H * Ts * Ts * 4 bytes fits 1 GiB.
+// The call runs ceil(B / cap) chunks of ceil(B / chunks) images (equal sizes: every chunk's GEMMs see the same row count; the last may be shorter).
+// A chunk runs the whole pass, so the activation buffers hold at most max(16384, mult * Ts) rows and the weights are read once per chunk.  No kernel of the
+// pass lets a row depend on its chunk-mates, and the window start is a multiple of 32 — the key block of flash64, a multiple of the 16-wide k-blocks of the
+// fp32 P·V product; the fp32 softmax sums a column in the thread of its absolute position — so leading masked columns add exact zeros: a sequence scored
+// alone returns the bits of its slice of any batch, in both modes, CFG pair included.
+#include "engine_internal.h"
+
+extern "C" {
+int car_score_nparts(int V);
+int car_launch_score(int mode, const ScoreP* p, float* nll, int* err_flag, hipStream_t st);
+void car_launch_score_embed(int mode, const void* emb, const int* tokens, void* h, int nseq, int ng, int n_new, int Ts, int Tv, int D, int V, int* err_flag, hipStream_t st);
+void car_launch_score_rope(int mode, void* qkv, const float* rope, int b, int Tn, int H, int dim, int t0, hipStream_t st);
+void car_launch_score_mask(const int64_t* emb_mask, unsigned char* out, int nseq, int ng, int img0, int T, int t0, int Tv, int Ts, hipStream_t st);
+}
+
+enum { kScoreRows = 16384 };                      // activation rows per chunk (the chunk rule above)
+static const size_t kScoreTensorCap = (size_t)1 << 30;
+
+static int ensure_host_flags(car_ctx* c) {
+    if (!c->host_flags) { HIPCHK(c, hipHostMalloc((void**)&c->host_flags, 64, hipHostMallocMapped)); memset(c->host_flags, 0, 64); }
+    return 0;
+}
+
+extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask, int32_t B, int32_t n_new, int32_t use_control,
+                         const car_sampling* sp, const int32_t* tokens, float* nll_out, float* logits_out, void* stream_) {
+    if (!c) return -1;
+    if (check_sticky(c)) return -1;
+    if (c->cfg.model_type != 0) FAIL(c, "car_score: context was created for the c2i model; scoring covers the t2i model only");
+    if (!c->finalized) FAIL(c, "car_score: call car_finalize_weights first");
+    if (!c->has_gpt) FAIL(c, "car_score: this context holds no GPT weights");
+    if (!text_emb || !sp || !tokens || !nll_out || B <= 0 || n_new <= 0) FAIL(c, "car_score: bad arguments");
+    if (text_dtype != CAR_DT_F32 && text_dtype != CAR_DT_BF16) FAIL(c, "car_score: text dtype must be F32 or BF16");
+    const car_config& g = c->cfg;
+    if (g.vocab_size % 4) FAIL(c, "car_score: vocab_size must be a multiple of 4");
+    const int T = g.cls_token_num;
+    if (n_new > g.block_size) FAIL(c, "car_score: %d tokens exceed block_size %d (rope table rows, gpt_t2i.py:454)", n_new, g.block_size);
+    if (use_control && (c->ctrl_B != B || c->ctrl_ntok < n_new)) FAIL(c, "car_score: control tokens cached for B=%d n=%d, requested B=%d n_new=%d (call car_encode_control first)", c->ctrl_B, c->ctrl_ntok, B, n_new);
+    const bool use_cfg = sp->cfg_scale > 1.0f;
+    const int mult = use_cfg ? 2 : 1, b = mult * B;
+    const float cs = use_cfg ? sp->control_strength : 1.0f;         // generate.py:87-92: strength ignored when cfg <= 1
+    const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok, li = g.n_layer / 3;
+    const int mode = c->mode; const size_t e = c->esz; const bool fast = mode == CAR_BF16;
+    if (D != Hn * 64) FAIL(c, "car_score: heads must be 64 wide");
+    hipStream_t caller = (hipStream_t)stream_, st = c->stream;
+    if (ensure_host_flags(c)) return -1;
+    int* err_flag = c->host_flags + 2;
+
+    fence_in(c, caller);
+    // ---- the prefill window of car_generate on the valid tail of the left-padded prompts, its start a multiple of 32 (see the chunk rule)
+    int Tv = T, t0 = 0;
+    if (emb_mask && T > 8 && T % 8 == 0 && (fast || T <= 128)) {
+        // scratch of its own (ws[9], the token loop's logits buffer, idle here): car_generate's device scalars stay as its car_get_stats expects them
+        NEED(c, c->ws[9], (size_t)(B + 4) * 4 + (size_t)B * T);
+        int* jmin = (int*)c->ws[9].p; int* jmin_min = jmin + B; unsigned char* mask_all = (unsigned char*)(jmin_min + 4);
+        car_launch_score_mask(emb_mask, mask_all, B, B, 0, T, 0, T, T, st);      // [B][T]: the whole prefix of every image
+        car_launch_mask_first_valid(mask_all, jmin, B, T, st);
+        int hmin = 0;
+        const bool hinted = sp->first_valid_hint > 0;
+        if (hinted) hmin = sp->first_valid_hint - 1;
+        else {      // no hint: ONE 4-byte read of the batch minimum, the call's only host wait (as car_generate)
+            car_launch_min_int(jmin, B, jmin_min, -1, nullptr, st);
+            HIPCHK(c, hipMemcpyAsync(&hmin, jmin_min, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+        }
+        const int hm = hmin < 0 ? 0 : (hmin > T ? T : hmin);
+        t0 = (hm / 32) * 32; if (t0 > T - 8) t0 = ((T - 8) / 32) * 32; if (t0 < 0) t0 = 0;
+        Tv = T - t0;
+        if (Tv % 8) { Tv = T; t0 = 0; }
+        if (hinted && t0 > 0) car_launch_min_int(jmin, B, jmin_min, t0, c->host_flags + 1, st);
+    }
+    const int Ts = Tv + n_new - 1, Tps = (int)rup((size_t)Ts, 32);
+    int nc = kScoreRows / (mult * Ts); if (nc < 1) nc = 1; if (nc > B) nc = B;
+    const bool pf_flash = use_flash(c, 64);
+    if (!pf_flash) while (nc > 1 && (size_t)nc * mult * Hn * Ts * Ts * 4 > kScoreTensorCap) --nc;
+    nc = (B + (B + nc - 1) / nc - 1) / ((B + nc - 1) / nc);      // the same number of chunks, of equal size (the last one may be shorter)
+    const int bc = mult * nc; const long rowsC = (long)bc * Ts;
+    const int nparts = car_score_nparts(V);
+
+    // ---- buffers (the prefill's workspaces, sized for one chunk)
+    NEED(c, c->ws[0], (size_t)bc * Tv * g.caption_dim * e);
+    NEED(c, c->ws[1], (size_t)rowsC * D * e);
+    NEED(c, c->ws[2], (size_t)rowsC * D * e);
+    NEED(c, c->ws[3], (size_t)rowsC * 3 * D * e);
+    { size_t s4 = use_control ? (size_t)B * n_tok * D * e : 0; if (!pf_flash) s4 = std::max(s4, (size_t)bc * Hn * Ts * Ts * 4); if (s4) NEED(c, c->ws[4], s4); }
+    if (!pf_flash) NEED(c, c->ws[5], (size_t)bc * Hn * Ts * Tps * e);
+    NEED(c, c->ws[6], (size_t)bc * D * Tps * e);
+    NEED(c, c->ws[7], (size_t)rowsC * (fast ? Fh : 3 * Fh) * e);
+    NEED(c, c->ws[8], (size_t)rowsC * D * e);
+    NEED(c, c->ws[10], (size_t)nparts * nc * n_new * 16);
+    NEED(c, c->maskw, (size_t)bc * Ts);
+    if (use_control) { NEED(c, c->ws[11], (size_t)B * n_tok * D * e); for (int k = 0; k < 3; ++k) NEED(c, c->ctrl[k], (size_t)b * n_tok * D * e); }
+    void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *P = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *att = c->ws[8].p;
+    float* S = (float*)c->ws[4].p;
+
+    // ---- C. control tokens of every chunk: condition_mlp, then the 3 condition_layers (gpt_t2i.py:437-442); rows [cond | zeros] per chunk
+    if (use_control) {
+        void* ce = c->ws[11].p; void* scratch = c->ws[4].p;
+        mlp_tanh(c, c->ctrl_in.p, D, 0, 1, B * n_tok, D, "condition_mlp.cap_proj.", scratch, ce, D, st);
+        for (int k = 0; k < 3; ++k) for (int i0 = 0; i0 < B; i0 += nc) {
+            const int ng = std::min(nc, B - i0); const size_t rows = (size_t)ng * n_tok, base = (size_t)mult * i0 * n_tok;
+            mlp_tanh(c, off(ce, (size_t)i0 * n_tok * D, e), D, 0, 1, (int)rows, D, "condition_layers." + std::to_string(k) + ".", scratch, off(c->ctrl[k].p, base * D, e), D, st);
+            if (use_cfg) HIPCHK(c, hipMemsetAsync(off(c->ctrl[k].p, (base + rows) * D, e), 0, rows * D * e, st));   // uncond rows: MLP(0) = 0 exactly
+        }
+    }
+    const long per_src = (long)T * g.caption_dim, per = (long)Tv * g.caption_dim; const size_t ib = text_dtype == CAR_DT_BF16 ? 2 : 4;
+    int rc = 0;
+    for (int i0 = 0; i0 < B; i0 += nc) {
+        const int ng = std::min(nc, B - i0), nseq = mult * ng; const long rows = (long)nseq * Ts, rowsW = (long)nseq * Tv;
+        // ---- D. input rows: the window of the text prefix (cls_embedding.cap_proj, gpt_t2i.py:435; uncond rows = uncond_embedding), then the token embeddings
+        car_launch_build_text(mode, (const char*)text_emb + (size_t)i0 * per_src * ib, text_dtype, Wp(c, "cls_embedding.uncond_embedding"), text, ng, per, per_src,
+                              (long)t0 * g.caption_dim, use_cfg, st);
+        mlp_tanh(c, text, g.caption_dim, 0, 1, (int)rowsW, g.caption_dim, "cls_embedding.cap_proj.", xn, att, D, st);
+        HIPCHK(c, hipMemcpy2DAsync(h, (size_t)Ts * D * e, att, (size_t)Tv * D * e, (size_t)Tv * D * e, (size_t)nseq, hipMemcpyDeviceToDevice, st));
+        car_launch_score_embed(mode, Wp(c, "tok_embeddings.weight"), tokens + (size_t)i0 * n_new, h, nseq, ng, n_new, Ts, Tv, D, V, err_flag, st);
+        car_launch_score_mask(emb_mask, (unsigned char*)c->maskw.p, nseq, ng, i0, T, t0, Tv, Ts, st);
+        const unsigned char* maskx = (const unsigned char*)c->maskw.p;
+        // ---- E. the layers over all Ts rows (gpt_t2i.py:446-470)
+        for (int l = 0; l < g.n_layer; ++l) {
+            const std::string L = "layers." + std::to_string(l) + ".";
+            {
+                NormP np; memset(&np, 0, sizeof(np));
+                np.h_in = h; np.h_out = h; np.xn = xn; np.w = Wp(c, L + "attention_norm.weight"); np.D = D; np.eps = g.norm_eps;
+                if (use_control && l % li == 0 && l / li < 3) {
+                    np.add_mode = 3; np.ctrl = off(c->ctrl[l / li].p, (size_t)mult * i0 * n_tok * D, e); np.T = Ts; np.row0 = Tv - 1; np.n_tok = n_tok; np.cs = cs;
+                }
+                car_launch_rmsnorm(mode, &np, rows, st);
+            }
+            { GemmP q = gp(xn, D, Wp(c, L + "attention.wqkv.weight"), D, qkv, 3 * D, (int)rows, 3 * D, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
+            car_launch_score_rope(mode, qkv, c->rope, nseq, Ts, Hn, D, t0, st);
+            car_launch_transpose_pad(mode, off(qkv, (size_t)2 * D, e), 3 * D, (long)Ts * 3 * D, vT, nseq, Ts, Tps, D, st);
+            bool fused = false;
+            if (pf_flash) {
+                FlashP f; memset(&f, 0, sizeof(f));
+                f.q = (const bf16_t*)qkv; f.k = (const bf16_t*)qkv + D; f.vt = (const bf16_t*)vT; f.o = (bf16_t*)att;
+                f.q_sb = f.k_sb = (long)Ts * 3 * D; f.q_st = f.k_st = 3 * D; f.vt_sb = (long)D * Tps; f.vt_ld = Tps; f.o_sb = (long)Ts * D; f.o_st = D;
+                f.Tq = f.Tk = Ts; f.H = Hn; f.scale = 0.125f; f.mode = 1; f.mask = maskx;
+                fused = car_launch_flash64(&f, nseq, st) == 0;
+                if (!fused) { rc = -2; break; }      // (the unfused buffers were not sized: flash64 takes every shape this pass builds)
+            } else {
+                GemmP q = gp(qkv, 3 * D, off(qkv, (size_t)D, e), 3 * D, S, Ts, Ts, Ts, 64);
+                q.alpha = 0.125f; q.out_f32 = 1; q.nb0 = nseq; q.nb1 = Hn;
+                q.sA0 = (long)Ts * 3 * D; q.sA1 = 64; q.sW0 = (long)Ts * 3 * D; q.sW1 = 64; q.sC0 = (long)Hn * Ts * Ts; q.sC1 = (long)Ts * Ts;
+                car_launch_gemm(mode, AMODE_PLAIN, &q, st);
+                car_launch_softmax_at(mode, S, Ts, P, Tps, (long)nseq * Hn * Ts, Ts, 1, maskx, Ts, Hn, t0, st);
+                GemmP r = gp(P, Tps, vT, Tps, att, D, Ts, 64, Tps);
+                r.nb0 = nseq; r.nb1 = Hn;
+                r.sA0 = (long)Hn * Ts * Tps; r.sA1 = (long)Ts * Tps; r.sW0 = (long)D * Tps; r.sW1 = (long)64 * Tps; r.sC0 = (long)Ts * D; r.sC1 = 64;
+                car_launch_gemm(mode, AMODE_PLAIN, &r, st);
+            }
+            { GemmP q = gp(att, D, Wp(c, L + "attention.wo.weight"), D, h, D, (int)rows, D, D); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
+            { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, L + "ffn_norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rows, st); }
+            if (fast) {
+                GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid, Fh, (int)rows, 2 * Fh, D); q.swiglu = 1; car_launch_gemm(mode, AMODE_PLAIN, &q, st);
+            } else {
+                void* mid2 = off(mid, (size_t)rows * Fh, e);
+                GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid2, 2 * Fh, (int)rows, 2 * Fh, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st);
+                car_launch_swiglu(mode, mid2, mid, rows, Fh, st);
+            }
+            { GemmP q = gp(mid, Fh, Wp(c, L + "feed_forward.w2.weight"), Fh, h, D, (int)rows, D, Fh); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
+        }
+        if (rc) break;
+        { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, "norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rows, st); }
+        // ---- the loss: rows Tv - 1 + i of every sequence against output.weight, the CFG pair mixed on the accumulators (score.hip)
+        ScoreP p; memset(&p, 0, sizeof(p));
+        p.x = xn; p.w = Wp(c, "output.weight"); p.targets = tokens + (size_t)i0 * n_new; p.part = (float*)c->ws[10].p;
+        p.logits = logits_out ? logits_out + (size_t)i0 * n_new * V : nullptr;
+        p.ldx = D; p.seq_stride = Ts; p.row_off = Tv - 1; p.unc_off = (long)ng * Ts; p.R = ng * n_new; p.V = V; p.D = D; p.rows_per_seq = n_new;
+        p.paired = use_cfg ? 1 : 0; p.round_bf16 = fast ? 1 : 0;      // fast mode: the logits are a bf16 linear's output widened to fp32 (gpt_t2i.py:470), as the decode step rounds them
+        p.cfg_interval = sp->cfg_interval; p.cfg_scale = sp->cfg_scale;
+        if (car_launch_score(mode, &p, nll_out + (size_t)i0 * n_new, err_flag, st)) { rc = -3; break; }
+    }
+    fence_out(c, caller);
+    if (rc == -2) FAIL(c, "car_score: the fused attention kernel rejected the pass's shape (dim=%d, rows per sequence=%d)", D, Ts);
+    if (rc == -3) FAIL(c, "car_score: the projection kernel rejected the model's shape (dim=%d must be a multiple of 32, vocab=%d of 4; 16-byte aligned outputs)", D, V);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// Runs score.hip's fused projection + cross-entropy alone (tests).  x [R,D] and w [V,D] in the context's element type, device.  Without pair_scale: targets
+// [R], nll [R], logits [R,V] or NULL.  With pair_scale [R/2] (R even): rows [0,R/2) are conditional, rows [R/2,R) their unconditional twins; targets, nll
+// and logits have R/2 rows.  Works on any context (no weights needed).
+extern "C" int car_debug_score_rows(car_ctx* c, const void* x, const void* w, const int32_t* targets, const float* pair_scale, int32_t R, int32_t V, int32_t D,
+                                    int32_t round_bf16, float* nll, float* logits, void* stream_) {
+    if (!c) return -1;
+    if (check_sticky(c)) return -1;
+    if (!x || !w || !targets || !nll || R <= 0 || V <= 0 || D <= 0) FAIL(c, "car_debug_score_rows: bad arguments");
+    if (pair_scale && (R & 1)) FAIL(c, "car_debug_score_rows: a pair scale needs an even number of rows");
+    if (ensure_host_flags(c)) return -1;
+    const int Ro = pair_scale ? R / 2 : R;
+    NEED(c, c->ws[10], (size_t)car_score_nparts(V) * Ro * 16);
+    hipStream_t caller = (hipStream_t)stream_, st = c->stream;
+    fence_in(c, caller);
+    ScoreP p; memset(&p, 0, sizeof(p));
+    p.x = x; p.w = w; p.targets = targets; p.scale = pair_scale; p.part = (float*)c->ws[10].p; p.logits = logits;
+    p.ldx = D; p.seq_stride = 0; p.row_off = 0; p.unc_off = Ro; p.R = Ro; p.V = V; p.D = D; p.rows_per_seq = Ro;
+    p.paired = pair_scale ? 1 : 0; p.round_bf16 = round_bf16 ? 1 : 0; p.cfg_interval = -1; p.cfg_scale = 1.f;
+    const int rc = car_launch_score(c->mode, &p, nll, c->host_flags + 2, st);
+    fence_out(c, caller);
+    if (rc) FAIL(c, "car_debug_score_rows: shape not supported (D %% %d, V %% 4, 16-byte aligned pointers)", c->mode == CAR_BF16 ? 32 : 16);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}

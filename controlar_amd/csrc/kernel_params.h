@@ -9,12 +9,31 @@
 //           parts: v = rnd(v + rnd(sum_s parts[s][r]))   (residual add of a dec_linear output, decode fast path)
 //           add_mode 1 (decode):  v = rnd(v + rnd(cs * ctrl[r, *pos - T + 1]))
 //           add_mode 2 (prefill): same with control token 0, only on rows r % T == T-1 (ctrl batch = r / T)
+//           add_mode 3 (score):   same with control token j = r % T - row0 on every row with j >= 0 (sequences of T rows: a window of the prefix, then
+//                                 the image tokens; row0 = the last prefix row; ctrl batch = r / T) — all positions of car_score's one pass
 //           h_out[r] = v (if h_out);  xn[r] = rnd(rnd(v * rsqrt(mean(v^2)+eps)) * w)
 struct NormP {
     const void* h_in; const void* emb; const int* idx; void* h_out; void* xn; const void* w;
     const void* ctrl; const int* pos; int add_mode; int T; int n_tok; float cs;
     int D; float eps;
     const float* parts; int parts_ks; long parts_stride;   // residual branch as fp32 split-K partials [ks][rows][D] of dec_linear
+    int row0;                                              // add_mode 3
+};
+
+// ------------------------------------------------------------------ fused vocabulary projection + cross-entropy (score.hip; car_score)
+// Output row r (an image position) takes its X row(s) from
+//     xrow(r, u) = (r / rows_per_seq) * seq_stride + row_off + r % rows_per_seq + u * unc_off        (u = 1: the unconditional row of a CFG pair)
+// logit[r][n] = x[xrow(r, 0)] . w[n]  (rounded to bf16 if round_bf16), and with `paired`
+//     logit[r][n] = s == 1 ? c : u + (c - u) * s,   s = scale ? scale[r] : (cfg_interval > -1 && r % rows_per_seq - 1 > cfg_interval ? 1 : cfg_scale)
+// The kernel leaves per row and per vocabulary part (max, sum of exp(logit - max), the target's logit or 0) in `part` [nparts][R][4]; score_fold_kernel
+// folds the parts in index order: nll[r] = max + log(sum) - logit[r][targets[r]].  logits (optional) [R][V] fp32 takes the same accumulators.
+struct ScoreP {
+    const void* x; const void* w; const int* targets; const float* scale;
+    float* part; float* logits;
+    long ldx, seq_stride, row_off, unc_off;
+    int R, V, D, rows_per_seq;
+    int paired, round_bf16, cfg_interval; float cfg_scale;
+    int nsplit, tiles_per_split;                           // vocabulary tiles (128 columns) per grid.y slice
 };
 
 struct SampleDyn { unsigned long long seed; float temperature; int top_k; float top_p; int pad; };

@@ -124,6 +124,7 @@ __global__ __launch_bounds__(1024) void rmsnorm_kernel(NormP p) {
     const T* add = nullptr;
     if (p.add_mode == 1) add = (const T*)p.ctrl + (r * p.n_tok + (*p.pos - p.T + 1)) * D;
     else if (p.add_mode == 2 && (r % p.T) == p.T - 1) add = (const T*)p.ctrl + ((r / p.T) * (long)p.n_tok) * D;
+    else if (p.add_mode == 3 && (r % p.T) >= p.row0) add = (const T*)p.ctrl + ((r / p.T) * (long)p.n_tok + (r % p.T - p.row0)) * D;
     float val[4][4];
     float ss = 0.f;
 #pragma unroll
@@ -210,9 +211,11 @@ __global__ __launch_bounds__(256) void softmax_kernel(const float* S, long lds, 
 }
 // Single pass, the row in registers (rows of up to 8 x 256 columns: the ViT encoder's 1025, the VQ AttnBlock's 1024): S is read once instead of three times.
 // Thread t owns columns t, t + 256, ... and sums them in that order, then block_sum — the statements of softmax_kernel, hence its bits.
+// `col0` (car_score's pass, col0 + ncols <= 2048): the absolute position of column 0; a column is then owned by the thread of its ABSOLUTE position, as in
+// softmax_wave_kernel, so a row's probabilities do not depend on where the batch-mates put the window.  col0 = 0 is the plain kernel.
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_reg_kernel(const float* S, long lds, void* P_, long ldp, int ncols, int mask_mode,
-                                                          const unsigned char* emb_mask, int Tq, int n_head) {
+                                                          const unsigned char* emb_mask, int Tq, int n_head, int col0) {
     __shared__ float sm[20];
     const long r = blockIdx.x;
     const float* s = S + r * lds; T* P = (T*)P_ + r * ldp;
@@ -222,8 +225,8 @@ __global__ __launch_bounds__(256) void softmax_reg_kernel(const float* S, long l
     float mx = -INFINITY;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int j = threadIdx.x + k * 256;
-        ok[k] = j < ncols && (!mask_mode || (j <= i && (mk[j] || j == i)));
+        const int j = threadIdx.x + k * 256 - col0;
+        ok[k] = j >= 0 && j < ncols && (!mask_mode || (j <= i && (mk[j] || j == i)));
         v[k] = ok[k] ? s[j] : 0.f;
         if (ok[k]) mx = fmaxf(mx, v[k]);
     }
@@ -234,7 +237,7 @@ __global__ __launch_bounds__(256) void softmax_reg_kernel(const float* S, long l
     sum = block_sum(sum, sm);
     const float inv = 1.0f / sum;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { const int j = threadIdx.x + k * 256; if (j < ldp) ET<T>::st(P + j, ok[k] ? v[k] * inv : 0.f); }
+    for (int k = 0; k < 8; ++k) { const int j = threadIdx.x + k * 256 - col0; if (j >= 0 && j < ldp) ET<T>::st(P + j, ok[k] ? v[k] * inv : 0.f); }
 }
 
 // Rows of at most 128 columns (the prefill's Tv x Tv scores): one WAVE per row, and a column is summed in the lane of its ABSOLUTE position col0 + j — lane
@@ -277,7 +280,8 @@ extern "C" void car_launch_softmax_at(int mode, const float* S, long lds, void* 
         else hipLaunchKernelGGL(softmax_wave_kernel<float>, g, dim3(256), 0, st, S, lds, P, ldp, rows, ncols, mask_mode, emb_mask, Tq, n_head, col0);
         return;
     }
-    if (ncols <= 2048 && ldp <= 2048) { LAUNCH_T(mode, softmax_reg_kernel, dim3(rows), dim3(256), st, S, lds, P, ldp, ncols, mask_mode, emb_mask, Tq, n_head); return; }
+    const int c0 = col0 > 0 ? col0 : 0;
+    if (c0 + ncols <= 2048 && c0 + ldp <= 2048) { LAUNCH_T(mode, softmax_reg_kernel, dim3(rows), dim3(256), st, S, lds, P, ldp, ncols, mask_mode, emb_mask, Tq, n_head, c0); return; }
     LAUNCH_T(mode, softmax_kernel, dim3(rows), dim3(256), st, S, lds, P, ldp, ncols, mask_mode, emb_mask, Tq, n_head);
 }
 extern "C" void car_launch_softmax(int mode, const float* S, long lds, void* P, long ldp, long rows, int ncols, int mask_mode,

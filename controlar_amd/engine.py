@@ -214,6 +214,79 @@ class Engine:
                         "car_generate")
         return (out, logits) if return_logits else out
 
+    def score(self, cond: torch.Tensor, tokens: torch.Tensor, emb_masks: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
+              cfg_interval: int = -1, use_control: bool = True, control_strength: float = 1.0, return_logits: bool = False,
+              first_valid: Optional[int] = None):
+        """Per-token negative log-likelihood of `tokens` [B,N] under the prompt `cond` (and the control of the preceding encode_control) in one parallel
+        pass (car_score): nll[b,i] = logsumexp(l_i) - l_i[tokens[b,i]] with l_i the logits row generate() would sample step i from after feeding back
+        tokens[b,:i] (after the CFG mix, before temperature / top-k / top-p).  Returns fp32 [B,N], or (nll, logits [B,N,V]) with return_logits.  The other
+        arguments mean what they mean to generate().  A token id outside [0, vocab) on a host tensor raises here; on a device tensor it raises the sticky
+        flag (check_errors)."""
+        if self.cfg.gpt.model_type == "c2i":
+            raise RuntimeError("car_score: context was created for the c2i model; scoring covers the t2i model only")
+        if not torch.is_tensor(cond) or cond.dim() != 3:
+            raise ValueError(f"score: cond must be [B,T,caption_dim], got {tuple(getattr(cond, 'shape', ()))}")
+        B, T, cap = cond.shape
+        if T != self.cfg.gpt.cls_token_num or cap != self.cfg.gpt.caption_dim:
+            raise ValueError(f"score: cond must be [B,{self.cfg.gpt.cls_token_num},{self.cfg.gpt.caption_dim}], got {tuple(cond.shape)}")
+        if not torch.is_tensor(tokens) or tokens.dim() != 2 or tokens.shape[0] != B or tokens.shape[1] < 1 or tokens.dtype.is_floating_point:
+            raise ValueError(f"score: tokens must be an integer tensor [B={B},N], got {tuple(getattr(tokens, 'shape', ()))}")
+        N = int(tokens.shape[1])
+        if tokens.device.type == "cpu":
+            lo, hi = int(tokens.min()), int(tokens.max())
+            if lo < 0 or hi >= self.cfg.gpt.vocab_size:
+                raise RuntimeError(f"car_score: token id out of range [0,{self.cfg.gpt.vocab_size}) (got {lo}..{hi})")
+        cond = cond.to(self.device)
+        if cond.dtype not in (torch.float32, torch.bfloat16):
+            cond = cond.float()
+        cond = cond.contiguous()
+        mask_t = None
+        if emb_masks is not None:
+            assert emb_masks.shape[0] == B and emb_masks.shape[-1] == T          # generate.py:185-186
+            if emb_masks.device.type == "cpu" and emb_masks.numel():
+                true_first = first_valid_position(emb_masks.reshape(B, T))
+                if first_valid is not None and int(first_valid) > true_first:
+                    raise RuntimeError(f"score: first_valid={int(first_valid)} is beyond the first valid prompt position of the batch ({true_first}): valid rows would be dropped")
+                if first_valid is None:
+                    first_valid = true_first
+            mask_t = emb_masks.to(device=self.device, dtype=torch.int64).contiguous()
+        sp = L.CarSampling()
+        sp.first_valid_hint = 0 if (first_valid is None or emb_masks is None) else max(0, min(int(first_valid), T)) + 1
+        sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), 1.0, 0
+        sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = 1.0, 0, 0, float(control_strength)
+        tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
+        nll = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        logits = torch.empty(B, N, self.cfg.gpt.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
+        self._check(self.lib.car_score(self._h, C.c_void_p(cond.data_ptr()), _dt(cond), C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0),
+                                       B, N, int(bool(use_control)), C.byref(sp), C.c_void_p(tok.data_ptr()), C.c_void_p(nll.data_ptr()),
+                                       C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())), "car_score")
+        return (nll, logits) if return_logits else nll
+
+    def score_rows(self, x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, pair_scale: Optional[torch.Tensor] = None,
+                   round_bf16: bool = False, return_logits: bool = False):
+        """The fused vocabulary projection + cross-entropy kernel alone (car_debug_score_rows; tests).  x [R,D], w [V,D] are converted to the context's
+        element type.  Without pair_scale: targets [R] -> nll [R].  With pair_scale [R/2]: rows [0,R/2) conditional, [R/2,R) unconditional, targets and
+        nll have R/2 rows."""
+        x = x.to(device=self.device, dtype=self.dtype).contiguous()
+        w = w.to(device=self.device, dtype=self.dtype).contiguous()
+        R, D = x.shape
+        V = w.shape[0]
+        assert w.shape[1] == D
+        Ro = R // 2 if pair_scale is not None else R
+        t = targets.to(device=self.device, dtype=torch.int32).contiguous()
+        assert t.numel() == Ro
+        ps = None
+        if pair_scale is not None:
+            ps = pair_scale.to(device=self.device, dtype=torch.float32).contiguous()
+            assert ps.numel() == Ro
+        nll = torch.empty(Ro, dtype=torch.float32, device=self.device)
+        logits = torch.empty(Ro, V, dtype=torch.float32, device=self.device) if return_logits else None
+        self._check(self.lib.car_debug_score_rows(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(t.data_ptr()),
+                                                  C.c_void_p(ps.data_ptr() if ps is not None else 0), R, V, D, int(bool(round_bf16)),
+                                                  C.c_void_p(nll.data_ptr()), C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                                  C.c_void_p(_stream_ptr())), "car_debug_score_rows")
+        return (nll, logits) if return_logits else nll
+
     def sample(self, logits: torch.Tensor, cfg_scale: float = 1.0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                sample_logits: bool = True, seed: int = 0, step: int = 0) -> torch.Tensor:
         """generate.py:59-74 sample() on caller-provided fp32 logits [rows, V] (rows = 2B under CFG) -> int32 [B]."""

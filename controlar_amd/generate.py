@@ -40,3 +40,35 @@ def generate(model: Transformer, cond, max_new_tokens, emb_masks=None, cfg_scale
                        top_p=float(sampling_kwargs.get("top_p", 1.0)), sample_logits=bool(sampling_kwargs.get("sample_logits", True)),
                        seed=_call_seed(sampling_kwargs))
     return out.to(cond.device)
+
+
+def score_loss(nll: torch.Tensor, valid=None) -> torch.Tensor:
+    """The loss Transformer.forward returns next to its logits (gpt_t2i.py:472-481), from per-token nll [B,N]: the mean, or with valid [B] the
+    valid-weighted sum over max(valid.sum() * N, 1) — the reference's (valid_all * loss_all).sum() / max(valid_all.sum(), 1) with valid repeated over
+    the N positions.  Reduced in fp64 on nll's device; a 0-d fp64 tensor."""
+    x = nll.to(torch.float64)
+    if valid is None:
+        return x.mean()
+    v = torch.as_tensor(valid).to(device=x.device, dtype=torch.float64).reshape(-1)
+    assert v.shape[0] == x.shape[0]
+    return (x * v[:, None]).sum() / torch.clamp(v.sum() * x.shape[1], min=1.0)
+
+
+@torch.no_grad()
+def score(model: Transformer, cond, tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, condition=None, control_strength=1, valid=None):
+    """Teacher-forced scoring with generate()'s argument conventions: Transformer.forward(idx, cond_idx, targets=tokens, valid=valid, condition=...)
+    evaluated in one parallel pass (car_score).  Returns (nll [B,N] fp32 on cond.device, loss): nll[b,i] = -log p(tokens[b,i] | prompt, control,
+    tokens[b,:i]) under the logits generate() samples from (after the CFG mix, before temperature / top-k / top-p); loss = score_loss(nll, valid)."""
+    if model.model_type != "t2i":
+        raise Exception("please check model type")          # scoring covers the t2i model
+    eng = model.engine
+    if condition is not None:
+        if isinstance(condition, _PendingControl):
+            condition = condition.img
+        eng.encode_control(condition)                       # model.adapter + model.adapter_mlp (generate.py:136-138)
+    if emb_masks is not None:
+        assert emb_masks.shape[0] == cond.shape[0] and emb_masks.shape[-1] == cond.shape[1]          # generate.py:185-186
+    nll = eng.score(cond, tokens, emb_masks, cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval), use_control=condition is not None,
+                    control_strength=float(control_strength))
+    loss = score_loss(nll, valid)
+    return nll.to(cond.device), loss.to(cond.device)

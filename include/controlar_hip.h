@@ -162,6 +162,26 @@ int car_generate(car_ctx* ctx, const void* text_emb, int32_t text_dtype, const i
                  int32_t* out_tokens, const int32_t* forced_tokens, float* logits_out, void* stream);
 
 /*
+ * score() — the per-token negative log-likelihood of GIVEN image tokens under a prompt and a control map, in one parallel pass: the `targets` branch of
+ * Transformer.forward (gpt_t2i.py:420-431,456-459,472-481) with generate()'s inference conventions.  Inputs mean what they mean to car_generate
+ * (text_emb, emb_mask: left-padded, folded into the causal mask, fully padded rows attend to themselves; use_control consumes the preceding
+ * car_encode_control; the prefill window on the valid tail, with the same single host read unless first_valid_hint is given).
+ *   tokens     [B,n_new] int32 (device): the sequence to score
+ *   nll_out    [B,n_new] fp32: logsumexp(l_i) - l_i[tokens[:,i]], where l_i is the fp32 logits row generate() hands to sample() at step i after feeding
+ *              back tokens[:, :i] — after the CFG mix uncond + (cond - uncond) * cfg_scale when cfg_scale > 1, with cfg_interval dropping the mix from
+ *              step cfg_interval + 2 on as the token loop does, before temperature / top-k / top-p
+ *   logits_out optional [B,n_new,vocab] fp32: the same l_i (the very accumulators nll_out was reduced from)
+ * Of `sp` only cfg_scale, cfg_interval, control_strength (ignored when cfg_scale <= 1, generate.py:87-92) and first_valid_hint are read.  No KV cache is
+ * written and nothing a later car_generate depends on is changed.  Images are scored in fixed chunks (engine_score.hip): a sequence scored alone returns
+ * the bits of its slice of a batch, in both modes.  Deterministic (no atomics).  A token id outside [0, vocab) cannot fail this call (no host
+ * read-back): it is read as token 0 and raises the sticky error flag, reported by the next entry on the context or by car_check_errors, as for the
+ * class labels of the c2i model.  c2i contexts are refused.
+ */
+int car_score(car_ctx* ctx, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask,
+              int32_t B, int32_t n_new, int32_t use_control, const car_sampling* sp,
+              const int32_t* tokens, float* nll_out, float* logits_out, void* stream);
+
+/*
  * Canny control extraction — replaces CannyDetector.__call__ = cv2.Canny(img, low, high) (condition/canny.py:6-14; callers
  * sample_t2i.py:123-125, sample_t2i_MR.py:139, demo 'Canny' preprocessor).  img: uint8 [B,H,W,3] (device).  edges_out: uint8 [B,H,W]
  * in {0,255} or NULL; control_out: [B,3,H,W] in the context's element type, = 2*(edges/255 - 0.5) replicated over 3 channels
@@ -404,6 +424,14 @@ int car_debug_f32_to_e4m3(const float* in, unsigned char* out, int64_t n);
 /* Host-only: the operand split of car_config.vq_split_bf16 on n values: hi[i] = round-to-nearest-even bf16 bits of x[i], lo[i] = RNE bf16 bits of
  * x[i] - float(hi[i]); where hi[i] is not finite (inf, NaN, or a value that rounds to inf) lo[i] is zero. */
 int car_debug_split_bf16(const float* x, int64_t n, uint16_t* hi, uint16_t* lo);
+
+/* Runs the fused vocabulary projection + cross-entropy kernel behind car_score alone (tests).  x [R,D] and w [V,D] in the context's element type, targets
+ * int32, all on the device; D a multiple of 32 (CAR_BF16) or 16 (CAR_F32), V of 4.  nll[r] = logsumexp_n(x[r] . w[n]) - x[r] . w[targets[r]]; logits
+ * (or NULL) takes the fp32 rows.  With pair_scale [R/2] (R even) rows [0,R/2) are conditional and rows [R/2,R) their unconditional twins, row r scores
+ * u + (c - u) * pair_scale[r] (a scale of exactly 1 takes c as it is), and targets, nll and logits have R/2 rows.  round_bf16 != 0 rounds every product
+ * row to bf16 first, as the CAR_BF16 model pass does.  Works on any context (no weights needed). */
+int car_debug_score_rows(car_ctx* ctx, const void* x, const void* w, const int32_t* targets, const float* pair_scale,
+                         int32_t R, int32_t V, int32_t D, int32_t round_bf16, float* nll, float* logits, void* stream);
 
 /* Copies the cached control tokens of layer-group k (0..2) [b,n_tok,dim] as fp32 to a HOST buffer (tests). */
 int car_debug_control_tokens(car_ctx* ctx, int32_t k, float* host_out, int64_t max_elems);
