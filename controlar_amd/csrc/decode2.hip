@@ -702,7 +702,7 @@ __global__ __launch_bounds__(NWAVE * 64) void dec_attn2_kernel(Attn2P p) {
             for (int j = lane; j < p.T; j += 64) { const int v = mk[j]; if (v != 0 && j < jm) jm = j; }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) jm = min(jm, __shfl_xor(jm, o, 64));
-            jmin = jm;
+            jmin = __builtin_amdgcn_readfirstlane(jm);      // every lane holds the minimum: scalar, so that load()'s edge test is a wave-uniform branch
         }
     }
     const int nblk = (pos >> 5) + 1, NW = p.nsplit * NWAVE;
@@ -722,10 +722,30 @@ __global__ __launch_bounds__(NWAVE * 64) void dec_attn2_kernel(Attn2P p) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) mb[e] = mk[min(jb + (e < 4 ? e : 12 + e), p.T - 1)];
         }
+        if (KV8) {
 #pragma unroll
-        for (int i = 0; i < (KV8 ? 2 : 4); ++i) kr[i] = __builtin_nontemporal_load(Kp + ((long)blk * (KV8 ? 2 : 4) + i) * 64);
+            for (int i = 0; i < 2; ++i) kr[i] = __builtin_nontemporal_load(Kp + ((long)blk * 2 + i) * 64);
 #pragma unroll
-        for (int i = 0; i < (KV8 ? 2 : 4); ++i) vr[i] = __builtin_nontemporal_load(Vp + ((long)blk * (KV8 ? 2 : 4) + i) * 64);
+            for (int i = 0; i < 2; ++i) vr[i] = __builtin_nontemporal_load(Vp + ((long)blk * 2 + i) * 64);
+        } else {
+            // rows of the block the sequence attends: [lo, hi] (scalars; blk comes from the wave index, the same in every lane).  An interior block takes all
+            // 32: every lane loads.  In the first and the last block of a sequence only the lanes that hold an attended row load (decode2_params.h
+            // attn2_edge_*): the others keep zeros — their scores are masked to -inf in compute(), their V elements meet an exact 0 probability, so the result
+            // keeps its bits and the 128-byte lines nobody needs stay in HBM.  One straight-line path for both kinds of block: a wave-uniform branch between
+            // an unpredicated and a predicated form made hipcc 7.2 merge the two register sets through copies (a wait on every load of the edge path, +28 VGPRs)
+            const int ub = __builtin_amdgcn_readfirstlane(blk) * 32;
+            const int lo = p.no_trim ? 0 : max(jmin, ub) - ub, hi = p.no_trim ? 31 : min(pos, ub + 31) - ub;
+            const bool k0 = attn2_edge_k_lane(0, lane, lo, hi), k1 = attn2_edge_k_lane(2, lane, lo, hi), vv = attn2_edge_v_lane(lane, lo, hi);
+            const u32x4 zu = (u32x4){0u, 0u, 0u, 0u};
+            u32x4 ka0 = zu, ka1 = zu, kb0 = zu, kb1 = zu, v0 = zu, v1 = zu, v2 = zu, v3 = zu;      // named values, stored whole below: partial stores into kr[] under two predicates came out as one 16-register tuple patched through copies
+            if (k0) { ka0 = __builtin_nontemporal_load(Kp + ((long)blk * 4 + 0) * 64); ka1 = __builtin_nontemporal_load(Kp + ((long)blk * 4 + 1) * 64); }
+            if (k1) { kb0 = __builtin_nontemporal_load(Kp + ((long)blk * 4 + 2) * 64); kb1 = __builtin_nontemporal_load(Kp + ((long)blk * 4 + 3) * 64); }
+            if (vv) {
+                v0 = __builtin_nontemporal_load(Vp + ((long)blk * 4 + 0) * 64); v1 = __builtin_nontemporal_load(Vp + ((long)blk * 4 + 1) * 64);
+                v2 = __builtin_nontemporal_load(Vp + ((long)blk * 4 + 2) * 64); v3 = __builtin_nontemporal_load(Vp + ((long)blk * 4 + 3) * 64);
+            }
+            kr[0] = ka0; kr[1] = ka1; kr[2] = kb0; kr[3] = kb1; vr[0] = v0; vr[1] = v1; vr[2] = v2; vr[3] = v3;
+        }
     };
     auto compute = [&](const u32x4 (&kr_)[4], const u32x4 (&vr_)[4], const unsigned (&mb)[8], int blk) {
         u32x4 kr[4], vr[4];

@@ -66,6 +66,14 @@ struct GemmDP {
 };
 
 // =============================================================================================== attention
+// Edge blocks of dec_attn2_kernel (bf16 cache): which lanes of the eight 1-KiB loads of a 32-position block hold a row the sequence attends.  [lo, hi] is the
+// attended range inside the block (0 <= lo, hi <= 31; empty if lo > hi).  A lane that holds none is not loaded (it gets zeros: its scores are masked to -inf and
+// its V elements meet an exact 0 probability).  The lane -> position maps are those of the packed layouts (decode2.hip header, the writers' kp / vp lines):
+//   K load i (0..3), lane l : position (i >> 1) * 16 + (l & 15), eight dims — a 128-byte line is 8 consecutive positions
+//   V load i (0..3), lane l : positions 4g..4g+3 and 16+4g..16+4g+3 of one dim, g = l >> 4 — a lane is needed if EITHER quartet meets the range
+__host__ __device__ inline bool attn2_edge_k_lane(int i, int lane, int lo, int hi) { const int t = (i >> 1) * 16 + (lane & 15); return t >= lo && t <= hi; }
+__host__ __device__ inline bool attn2_edge_v_lane(int lane, int lo, int hi) { const int a = (lane >> 4) * 4; return (a <= hi && a + 3 >= lo) || (a + 16 <= hi && a + 19 >= lo); }
+
 struct Attn2P {
     const bf16_t* q;            // [b][H][64] rotated, pre-scaled (EPI_QKV)
     const bf16_t* kc; const bf16_t* vc;   // packed caches of this layer (chain base)
@@ -76,7 +84,8 @@ struct Attn2P {
     float* part;                // nsplit > 1: [b][H][nsplit][66] (m, l, o[64])
     int H, SA, T, dim, nsplit, out_packed;
     int kv8;                    // the caches hold e4m3 bytes (K8 / V8 layouts), widened to bf16 in registers
-    int n_seq, pgrid;           // persistent form (nsplit == 1): n_seq > 0 sequences, a 1-D grid of pgrid workgroups walks the n_seq*H items
+    int no_trim;                // A/B (wave-uniform): edge blocks load all 32 rows like interior ones instead of only the lanes with rows in [jmin, pos]
+    int n_seq, pgrid;          // persistent form (nsplit == 1): n_seq > 0 sequences, a 1-D grid of pgrid workgroups walks the n_seq*H items
     CAR_PF_FIELDS               // helpers need the 1-D (persistent) grid: pgrid = n_seq * H + pf_wgs
     CAR_STAMP_FIELDS
 };

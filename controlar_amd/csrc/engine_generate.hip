@@ -12,7 +12,7 @@
 enum { RA_NONE = 0, RA_SMALL, RA_NX, RA_MID, kEarlyChain = 8, kNoOverride = -0x7fffffff };      // RA_*: L2 run-ahead form of a chain (plan_decode)
 struct ChainPlan {
     int b0, bg, nsplit;
-    int attn_variant, attn_lds_pad, attn_pgrid;      // attn_variant: the decode2.hip variant (fast) / the `fused` form of car_launch_dec_attn_f32_ex (exact)
+    int attn_variant, attn_lds_pad, attn_pgrid, attn_no_trim;      // attn_no_trim: A/B, dec_attn2 loads whole edge blocks (Attn2P::no_trim); attn_variant: the decode2.hip variant (fast) / the `fused` form of car_launch_dec_attn_f32_ex (exact)
     int fuse_norm, normx, normx_max, normx_j4, staged_normx;      // the norms: GEMM prologue (<= 8 rows) / on the fly (<= normx_max rows; staged = NORM == 3 allowed) / rmsnorm2 launches
     int runahead, kv_runahead;                       // RA_*; the KV prefixes ride on w2's helpers (MEASURED, OFF)
 };
@@ -36,6 +36,7 @@ static void plan_decode(DecodePlan& pl, const car_config& g, int mode, int n_cu,
     const char *k_chains = CAR_KNOB("CAR_CHAINS"), *k_one_max = CAR_KNOB("CAR_ONE_LAUNCH_MAX"), *k_variant = CAR_KNOB("CAR_ATTN_VARIANT"), *k_phase = CAR_KNOB("CAR_PHASE_OFFSET"), *k_form = CAR_KNOB("CAR_ATTN_F32_FORM");
     const bool single_chain = CAR_KNOB("CAR_SINGLE_CHAIN"), no_early = CAR_KNOB("CAR_NO_EARLY_CHAIN"), split_small = CAR_KNOB("CAR_ATTN_SPLIT_SMALL"), old_small = CAR_KNOB("CAR_ATTN_OLD_SMALL");
     const bool no_runahead = CAR_KNOB("CAR_NO_RUNAHEAD"), no_small_fuse = CAR_KNOB("CAR_NO_SMALL_FUSE"), no_normx = CAR_KNOB("CAR_NO_NORMX"), kv_runahead = CAR_KNOB("CAR_KV_RUNAHEAD"), no_staged = CAR_KNOB("CAR_NO_STAGED_NORMX");
+    const bool attn_no_trim = CAR_KNOB("CAR_ATTN_NO_TRIM");      // A/B: the attention's edge blocks stream all 32 rows (profiles/attn_trim_ab.txt)
     const int k_nsplit = num(CAR_KNOB("CAR_ATTN_NSPLIT"), 0), k_persist = num(CAR_KNOB("CAR_ATTN_PERSIST"), 0), lds_pad = num(CAR_KNOB("CAR_ATTN_LDS_PAD"), 0);      // A/B: shorter attention workgroups / persistent grid
     const int normx_max = num(CAR_KNOB("CAR_NORMX_MAX"), 48), normx_j4 = num(CAR_KNOB("CAR_NORMX_J4"), 0) != 0, k_gsteps = num(CAR_KNOB("CAR_GRAPH_STEPS"), 1);
     pl.mode = mode; pl.mult = mult; pl.lin_prio = num(CAR_KNOB("CAR_LINEAR_PRIO"), 0) != 0;
@@ -82,7 +83,7 @@ static void plan_decode(DecodePlan& pl, const car_config& g, int mode, int n_cu,
         // attention variant (decode2.hip; profiles/r02_kbench_*): 4 waves per (sequence, head) from 128 sequences up, 2 below; 16 in the one-launch small form
         // (round 6: the one-launch form is dec_attn2s_kernel, variant 162 — two blocks in flight per wave, bit-identical to 160; it needs T <= 512 and the jmin table)
         cp.attn_variant = (one_launch && cp.nsplit == 1) ? ((T <= 512 && !old_small) ? 162 : 160) : ((cp.nsplit == 1 && bg < 128) ? 20 : 40);
-        cp.attn_variant = num(k_variant, cp.attn_variant); cp.attn_lds_pad = lds_pad;
+        cp.attn_variant = num(k_variant, cp.attn_variant); cp.attn_lds_pad = lds_pad; cp.attn_no_trim = attn_no_trim;
         // persistent attention grid: R resident workgroups per CU walk the (sequence, head) items in equal shares
         if (k_persist > 0 && k_persist <= 16 && cp.nsplit == 1) { const long items = (long)bg * Hn, cap = (long)n_cu * k_persist;
             if (items > cap) { const long per = (items + cap - 1) / cap; cp.attn_pgrid = (int)((items + per - 1) / per); }
@@ -232,7 +233,7 @@ static int enqueue_decode_step_fast(car_ctx* c, const StepBufs& sb, const Decode
         {
             Attn2P ap; memset(&ap, 0, sizeof(ap));
             ap.q = fb.q; ap.kc = kc; ap.vc = vc; ap.pos = cb.pos; ap.mask = sb.maskb ? sb.maskb + (size_t)b0 * T : nullptr; ap.jmin = sb.jmin ? sb.jmin + b0 : nullptr;
-            ap.out = fb.att; ap.part = fb.attn_part; ap.H = Hn; ap.SA = SA; ap.T = T; ap.dim = D; ap.nsplit = nsplit; ap.out_packed = 1; ap.kv8 = g.kv_cache_fp8 ? 1 : 0;
+            ap.out = fb.att; ap.part = fb.attn_part; ap.H = Hn; ap.SA = SA; ap.T = T; ap.dim = D; ap.nsplit = nsplit; ap.out_packed = 1; ap.kv8 = g.kv_cache_fp8 ? 1 : 0; ap.no_trim = cp.attn_no_trim;
             if (cp.attn_pgrid > 0 && nsplit == 1) { ap.n_seq = b; ap.pgrid = cp.attn_pgrid; }
             if (cp.attn_variant == 162) {      // the small-batch kernel hosts the run-ahead for wo and w1|w3
                 ap.pf_wgs = helpers_for(ra_lin, b * Hn);
@@ -335,6 +336,16 @@ static int enqueue_decode_step(car_ctx* c, const StepBufs& sb, const DecodePlan&
     SampleP sp = cb.sp; sp.logits = logits; sp.step_ptr = cb.step; car_launch_sample_greedy(&sp, st); ++nk;
     c->n_dec_kernels = nk;
     if (bad) FAIL(c, "exact-mode decode GEMM: tile configuration %d rejected (b=%d, dim=%d, ffn=%d, vocab=%d: N %% 32 and K %% 16 must be 0)", bad, b, D, Fh, V);
+    return 0;
+}
+
+// host-only view of the edge-block lane predicates of dec_attn2_kernel (decode2_params.h attn2_edge_*; tests/test_attn_trim_cpu.py)
+extern "C" int car_debug_attn_edge_mask(int32_t lo, int32_t hi, unsigned char* k_mask, unsigned char* v_mask) {
+    if (!k_mask || !v_mask || lo < 0 || hi > 31 || lo > hi) return -1;
+    for (int i = 0; i < 4; ++i) for (int l = 0; l < 64; ++l) {
+        k_mask[i * 64 + l] = attn2_edge_k_lane(i, l, lo, hi) ? 1 : 0;
+        v_mask[i * 64 + l] = attn2_edge_v_lane(l, lo, hi) ? 1 : 0;
+    }
     return 0;
 }
 

@@ -433,6 +433,11 @@ int car_debug_split_bf16(const float* x, int64_t n, uint16_t* hi, uint16_t* lo);
 int car_debug_score_rows(car_ctx* ctx, const void* x, const void* w, const int32_t* targets, const float* pair_scale,
                          int32_t R, int32_t V, int32_t D, int32_t round_bf16, float* nll, float* logits, void* stream);
 
+/* Host-only: the lane predicates of the bf16 decode attention's edge blocks.  [lo, hi] (0 <= lo <= hi <= 31) is the range of attended rows inside one
+ * 32-position block of the packed KV cache; k_mask[i*64 + l] / v_mask[i*64 + l] = 1 if lane l of the block's i-th 1-KiB K / V load (i = 0..3) is issued,
+ * 0 if the lane holds no attended row and gets zeros instead.  Non-zero on a range outside those bounds. */
+int car_debug_attn_edge_mask(int32_t lo, int32_t hi, unsigned char* k_mask /* [4*64] */, unsigned char* v_mask /* [4*64] */);
+
 /* Copies the cached control tokens of layer-group k (0..2) [b,n_tok,dim] as fp32 to a HOST buffer (tests). */
 int car_debug_control_tokens(car_ctx* ctx, int32_t k, float* host_out, int64_t max_elems);
 
