@@ -102,6 +102,18 @@ __device__ inline float silu_f(float x) { return x / (1.0f + expf(-x)); }
 enum { ACT_NONE = 0, ACT_GELU_ERF = 1, ACT_GELU_TANH = 2, ACT_SILU = 3 };
 enum { BIAS_NONE = 0, BIAS_N = 1, BIAS_M = 2 };
 enum { AMODE_PLAIN = 0, AMODE_CONV3 = 1, AMODE_CONV3S2 = 2 };
+// what car_gemm_route (gemm.hip) answers: the kernel family a descriptor takes through car_launch_gemm, or (negative) why the launcher refuses it
+enum CarGemmRoute {
+    CAR_ROUTE_BF16_REG = 0,       // gemm_bf16_kernel: 128x128x32, register-staged
+    CAR_ROUTE_BF16_GLDS = 1,      // gemm_bf16_glds_kernel: 256x128x64, LDS-DMA ring
+    CAR_ROUTE_HALO64 = 2,         // conv3_halo64_kernel
+    CAR_ROUTE_HALO128 = 3,        // conv3_halo_kernel (development switch CAR_CONV_HALO128)
+    CAR_ROUTE_F32_SPLIT = 4,      // gemm_f32s_kernel (GemmP::split3)
+    CAR_ROUTE_F32_MFMA = 5,       // gemm_f32_mfma_kernel
+    CAR_ROUTE_F32_VALU = 6,       // gemm_f32_kernel
+    CAR_ROUTE_REFUSE_GN = -1,     // GemmP::gn_part on a call that cannot take conv3_halo64_kernel
+    CAR_ROUTE_REFUSE_K = -3       // K no multiple of the kernels' step: bf16 32, fp32 16
+};
 
 // Generic GEMM descriptor: C[z][m,n] = epi( alpha * sum_k A[z][m,k] * W[z][n,k] )   (both K-contiguous)
 struct GemmP {

@@ -45,7 +45,7 @@ void car_launch_t5_softmax(int mode, const float* S, long lds, void* P, long ldp
                            const unsigned char* mask, int Tq, int n_head, hipStream_t st);
 void car_launch_t5_gated_act(int mode, const void* in, void* out, long rows, int hidden, hipStream_t st);
 int car_launch_flash64(const FlashP* p, int B, hipStream_t st);
-int car_launch_gemm(int mode, int amode, const GemmP* p, hipStream_t st);   // -1: GemmP::gn_part on a call that cannot take conv3_halo64_kernel (nothing launched)
+int car_launch_gemm(int mode, int amode, const GemmP* p, hipStream_t st);   // -1: GemmP::gn_part on a call that cannot take conv3_halo64_kernel; -3: K no multiple of the kernels' step (bf16 32, fp32 16) — nothing launched (car_gemm_route)
 int car_conv3_halo64_ok(int mode, const GemmP* p);
 void car_launch_convert(int mode, const void* src, int src_dtype, void* dst, long n, hipStream_t st);
 void car_launch_build_text(int mode, const void* cond, int src_dtype, const void* uncond, void* dst, int B, long per, long per_src, long src_off, int use_cfg, hipStream_t st);

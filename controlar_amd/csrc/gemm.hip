@@ -403,7 +403,7 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(GemmP p) {
     const int ec = (lane & 7) * 8, en = n0 + wn * 64 + ec;
     float bv[8];
     {
-        const uint4 u = bias ? *(const uint4*)(bias + en) : make_uint4(0, 0, 0, 0);
+        const uint4 u = p.bias_mode == BIAS_N ? *(const uint4*)(bias + en) : make_uint4(0, 0, 0, 0);      // as epi_value: the mode decides, not the pointer
         const unsigned w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) { bv[2 * e] = __uint_as_float(w[e] << 16); bv[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(512, 4) void conv3_halo64_kernel(GemmP p) {
     const int ec = (lane & 7) * 8, en = n0 + wn * 64 + ec;
     float bv[8];
     {
-        const uint4 u = bias ? *(const uint4*)(bias + en) : make_uint4(0, 0, 0, 0);
+        const uint4 u = p.bias_mode == BIAS_N ? *(const uint4*)(bias + en) : make_uint4(0, 0, 0, 0);      // as epi_value: the mode decides, not the pointer
         const unsigned w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) { bv[2 * e] = __uint_as_float(w[e] << 16); bv[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
@@ -766,92 +766,124 @@ static bool conv3_halo_plan(int mode, int amode, const GemmP& p, int* dev_out, v
 extern "C" int car_conv3_halo64_ok(int mode, const GemmP* pp) {
     return conv3_halo_plan(mode, AMODE_CONV3, *pp, nullptr, nullptr) && !CAR_KNOB("CAR_CONV_HALO128") && !CAR_KNOB("CAR_GN_UNFUSED");
 }
-// returns 0, or -1 when GemmP::gn_part is set on a call that cannot take conv3_halo64_kernel (the caller did not ask car_conv3_halo64_ok): nothing is launched;
-// -2 when the split kernel's launch set-up failed (GemmP::split3; the dynamic-LDS attribute): nothing is launched either
+// THE routing decision of car_launch_gemm, side-effect free except for the zero page of the LDS-DMA loaders: which kernel family a descriptor takes (CarGemmRoute,
+// car_common.h), or why it is refused.  car_launch_gemm switches on it, so a harness that asserts a route (experiments/gemm_check.hip) and the launcher cannot disagree.
+//   CAR_ROUTE_REFUSE_GN (-1)  GemmP::gn_part on a call that cannot take conv3_halo64_kernel (the caller did not ask car_conv3_halo64_ok)
+//   CAR_ROUTE_REFUSE_K  (-3)  K outside the kernels' contract: every bf16 kernel walks K in steps of 32 (the LDS-DMA ones of 64, chosen only when K % 64 == 0),
+//                             every fp32 kernel in steps of 16 — a ragged K would silently drop its tail
 extern "C" int car_gemm_split_ok(int amode, const GemmP* pp);                                   // gemm_split.hip
 extern "C" hipError_t car_launch_gemm_split(int amode, const GemmP* pp, hipStream_t st);
+extern "C" int car_gemm_route(int mode, int amode, const GemmP* pp) {
+    const GemmP& p = *pp;
+    const int nb0 = p.nb0 <= 0 ? 1 : p.nb0, nb1 = p.nb1 <= 0 ? 1 : p.nb1;
+    if (mode == 1) {
+        // 3x3 conv with the input halo resident in LDS: stride 1, optional folded x2 upsample (K == 9 * Cin, Cin % 128 == 0: inside the K contract)
+        if (conv3_halo_plan(mode, amode, p, nullptr, nullptr)) {
+            const bool halo128 = CAR_KNOB("CAR_CONV_HALO128") != nullptr;
+            if (p.gn_part && (halo128 || CAR_KNOB("CAR_GN_UNFUSED"))) return CAR_ROUTE_REFUSE_GN;
+            return halo128 ? CAR_ROUTE_HALO128 : CAR_ROUTE_HALO64;      // default: the 75-KB form, two workgroups per CU (A/B switch: CAR_CONV_HALO128=1 -> the 131-KB kernel)
+        }
+        if (p.gn_part) return CAR_ROUTE_REFUSE_GN;
+        if (p.K % BKK != 0) return CAR_ROUTE_REFUSE_K;
+        const bool al16 = ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.W % 16 == 0) && p.ldw % 8 == 0 && p.sW0 % 8 == 0 && p.sW1 % 8 == 0 && p.sA0 % 8 == 0 && p.sA1 % 8 == 0;
+        const long tiles = (long)((p.N + BN - 1) / BN) * ((p.M + G2_BM - 1) / G2_BM) * nb0 * nb1;
+        int dev = 0; (void)hipGetDevice(&dev);
+        const bool ok2 = dev >= 0 && dev < 16 && p.K % G2_BK == 0 && p.K >= 512 && al16 && tiles >= 512 && !CAR_KNOB("CAR_GEMM_V1") &&
+                         (amode == AMODE_PLAIN ? p.lda % 8 == 0 : (amode == AMODE_CONV3 && p.Cin % G2_BK == 0));
+        return ok2 ? CAR_ROUTE_BF16_GLDS : CAR_ROUTE_BF16_REG;
+    }
+    if (p.gn_part) return CAR_ROUTE_REFUSE_GN;    // GroupNorm partials are a bf16 conv3_halo64_kernel feature
+    if (p.K % 16 != 0) return CAR_ROUTE_REFUSE_K;
+    // opt-in split-bf16 arithmetic (gemm_split.hip): three bf16 MFMAs per fp32 product where the one predicate holds; every other call is exact fp32 as below
+    if (p.split3 && car_gemm_split_ok(amode, &p)) return CAR_ROUTE_F32_SPLIT;
+    // exact mode: fp32 MFMA tiles (16 x the VALU rate per CU); the round-1 VALU kernel serves the shapes whose strides break the loader's 16-byte chunks.
+    // (For a convolution with K == 9 * Cin the K contract above already implies Cin % 16 == 0; the Cin term only guards a descriptor whose K is not 9 * Cin.)
+    const bool mfma_ok = p.ldw % 4 == 0 && ((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.W & 15) == 0 && p.sA0 % 4 == 0 && p.sA1 % 4 == 0 && p.sW0 % 4 == 0 && p.sW1 % 4 == 0 &&
+                         (amode == AMODE_PLAIN ? p.lda % 4 == 0 : p.Cin % 4 == 0);
+    return mfma_ok ? CAR_ROUTE_F32_MFMA : CAR_ROUTE_F32_VALU;
+}
+// returns 0, or the negative route of car_gemm_route (-1, -3): nothing is launched;
+// -2 when the split kernel's launch set-up failed (GemmP::split3; the dynamic-LDS attribute): nothing is launched either
 extern "C" int car_launch_gemm(int mode, int amode, const GemmP* pp, hipStream_t st) {
     GemmP p = *pp;
     if (p.nb0 <= 0) p.nb0 = 1;
     if (p.nb1 <= 0) p.nb1 = 1;
-    if (mode == 1) {
-        if (amode != AMODE_CONV3 || (p.Ho & 15) || (p.Wo & 15) || CAR_KNOB("CAR_CONV_LINEAR")) p.patch = 0;
-        dim3 g((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.nb0 * p.nb1);
-        // dynamic-LDS attributes are per device (a one-process multi-GPU host launches on several)
-        static bool attr_set[16] = {}, attr3[16] = {}, attr4[16] = {};
-        int dev = 0; void* zero = nullptr;
-        // 3x3 conv with the input halo resident in LDS: stride 1, optional folded x2 upsample
-        if (conv3_halo_plan(mode, amode, p, &dev, &zero)) {
-            p.zero = zero;
-            const dim3 g3((p.N + BN - 1) / BN, (unsigned)((long)p.M / 256));
-            const bool halo128 = CAR_KNOB("CAR_CONV_HALO128") != nullptr;
-            if (p.gn_part && (halo128 || CAR_KNOB("CAR_GN_UNFUSED"))) return -1;
-            if (!halo128) {          // default: the 75-KB form, two workgroups per CU (A/B switch: CAR_CONV_HALO128=1 -> the 131-KB kernel)
-                const size_t sh4 = (size_t)(CH64_HALO_PIX * 64 + 2 * BN * G2_BK) * 2;
-                if (!attr4[dev]) {
-                    (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
-                    (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
-                    (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
-                    (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
-                    attr4[dev] = true;
-                }
-                if (p.ups == 0) { if (p.gn_part) hipLaunchKernelGGL((conv3_halo64_kernel<0, 1>), g3, dim3(512), sh4, st, p); else hipLaunchKernelGGL((conv3_halo64_kernel<0, 0>), g3, dim3(512), sh4, st, p); }
-                else { if (p.gn_part) hipLaunchKernelGGL((conv3_halo64_kernel<1, 1>), g3, dim3(512), sh4, st, p); else hipLaunchKernelGGL((conv3_halo64_kernel<1, 0>), g3, dim3(512), sh4, st, p); }
-                return 0;
-            }
-            const size_t sh3 = (size_t)(CH_HALO_MAX * 128 + 3 * BN * G2_BK) * 2;
-            if (!attr3[dev]) {
-                (void)hipFuncSetAttribute((const void*)conv3_halo_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh3);
-                (void)hipFuncSetAttribute((const void*)conv3_halo_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh3);
-                attr3[dev] = true;
-            }
-            if (p.ups == 0) hipLaunchKernelGGL(conv3_halo_kernel<0>, g3, dim3(512), sh3, st, p);
-            else hipLaunchKernelGGL(conv3_halo_kernel<1>, g3, dim3(512), sh3, st, p);
+    const int route = car_gemm_route(mode, amode, &p);
+    if (route < 0) {
+        if (route == CAR_ROUTE_REFUSE_K) fprintf(stderr, "car_launch_gemm: K = %d is not a multiple of %d (%s kernels): refused, nothing launched\n", p.K, mode == 1 ? BKK : 16, mode == 1 ? "bf16" : "fp32");
+        return route;
+    }
+    // dynamic-LDS attributes are per device (a one-process multi-GPU host launches on several)
+    static bool attr_set[16] = {}, attr3[16] = {}, attr4[16] = {};
+    int dev = 0; (void)hipGetDevice(&dev);
+    if (mode == 1) { if (amode != AMODE_CONV3 || (p.Ho & 15) || (p.Wo & 15) || CAR_KNOB("CAR_CONV_LINEAR")) p.patch = 0; }
+    else p.patch = 0;                             // the exact-mode kernels enumerate pixels linearly
+    switch (route) {
+    case CAR_ROUTE_HALO64: {
+        p.zero = zero_page_for(dev);              // non-null: conv3_halo_plan said yes
+        const dim3 g3((p.N + BN - 1) / BN, (unsigned)((long)p.M / 256));
+        const size_t sh4 = (size_t)(CH64_HALO_PIX * 64 + 2 * BN * G2_BK) * 2;
+        if (!attr4[dev]) {
+            (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
+            (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
+            (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
+            (void)hipFuncSetAttribute((const void*)conv3_halo64_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh4);
+            attr4[dev] = true;
+        }
+        if (p.ups == 0) { if (p.gn_part) hipLaunchKernelGGL((conv3_halo64_kernel<0, 1>), g3, dim3(512), sh4, st, p); else hipLaunchKernelGGL((conv3_halo64_kernel<0, 0>), g3, dim3(512), sh4, st, p); }
+        else { if (p.gn_part) hipLaunchKernelGGL((conv3_halo64_kernel<1, 1>), g3, dim3(512), sh4, st, p); else hipLaunchKernelGGL((conv3_halo64_kernel<1, 0>), g3, dim3(512), sh4, st, p); }
+        return 0;
+    }
+    case CAR_ROUTE_HALO128: {
+        p.zero = zero_page_for(dev);
+        const dim3 g3((p.N + BN - 1) / BN, (unsigned)((long)p.M / 256));
+        const size_t sh3 = (size_t)(CH_HALO_MAX * 128 + 3 * BN * G2_BK) * 2;
+        if (!attr3[dev]) {
+            (void)hipFuncSetAttribute((const void*)conv3_halo_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh3);
+            (void)hipFuncSetAttribute((const void*)conv3_halo_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh3);
+            attr3[dev] = true;
+        }
+        if (p.ups == 0) hipLaunchKernelGGL(conv3_halo_kernel<0>, g3, dim3(512), sh3, st, p);
+        else hipLaunchKernelGGL(conv3_halo_kernel<1>, g3, dim3(512), sh3, st, p);
+        return 0;
+    }
+    case CAR_ROUTE_BF16_GLDS: {
+        const size_t sh = (size_t)G2_NS * G2_STAGE * 2;
+        if (!attr_set[dev]) {
+            (void)hipFuncSetAttribute((const void*)gemm_bf16_glds_kernel<AMODE_PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+            (void)hipFuncSetAttribute((const void*)gemm_bf16_glds_kernel<AMODE_CONV3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+            attr_set[dev] = true;
+        }
+        if ((p.zero = zero_page_for(dev)) != nullptr) {
+            dim3 g2((p.N + BN - 1) / BN, (p.M + G2_BM - 1) / G2_BM, p.nb0 * p.nb1);
+            if (amode == AMODE_PLAIN) hipLaunchKernelGGL(gemm_bf16_glds_kernel<AMODE_PLAIN>, g2, dim3(512), sh, st, p);
+            else hipLaunchKernelGGL(gemm_bf16_glds_kernel<AMODE_CONV3>, g2, dim3(512), sh, st, p);
             return 0;
         }
-        if (p.gn_part) return -1;
-        const bool al16 = ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.W % 16 == 0) && p.ldw % 8 == 0 && p.sW0 % 8 == 0 && p.sW1 % 8 == 0 && p.sA0 % 8 == 0 && p.sA1 % 8 == 0;
-        const long tiles = (long)((p.N + BN - 1) / BN) * ((p.M + G2_BM - 1) / G2_BM) * p.nb0 * p.nb1;
-        (void)hipGetDevice(&dev);
-        const bool ok2 = dev >= 0 && dev < 16 && p.K % G2_BK == 0 && p.K >= 512 && al16 && tiles >= 512 && !CAR_KNOB("CAR_GEMM_V1") &&
-                         (amode == AMODE_PLAIN ? p.lda % 8 == 0 : (amode == AMODE_CONV3 && p.Cin % G2_BK == 0));
-        if (ok2) {
-            const size_t sh = (size_t)G2_NS * G2_STAGE * 2;
-            if (!attr_set[dev]) {
-                (void)hipFuncSetAttribute((const void*)gemm_bf16_glds_kernel<AMODE_PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-                (void)hipFuncSetAttribute((const void*)gemm_bf16_glds_kernel<AMODE_CONV3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-                attr_set[dev] = true;
-            }
-            if ((zero = zero_page_for(dev)) != nullptr) {
-                p.zero = zero;
-                dim3 g2((p.N + BN - 1) / BN, (p.M + G2_BM - 1) / G2_BM, p.nb0 * p.nb1);
-                if (amode == AMODE_PLAIN) hipLaunchKernelGGL(gemm_bf16_glds_kernel<AMODE_PLAIN>, g2, dim3(512), sh, st, p);
-                else hipLaunchKernelGGL(gemm_bf16_glds_kernel<AMODE_CONV3>, g2, dim3(512), sh, st, p);
-                return 0;
-            }
-        }
+        [[fallthrough]];                          // no zero page: the register-staged kernel needs none
+    }
+    case CAR_ROUTE_BF16_REG: {
+        dim3 g((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.nb0 * p.nb1);
         if (amode == AMODE_PLAIN) hipLaunchKernelGGL(gemm_bf16_kernel<AMODE_PLAIN>, g, dim3(256), 0, st, p);
         else if (amode == AMODE_CONV3S2) hipLaunchKernelGGL(gemm_bf16_kernel<AMODE_CONV3S2>, g, dim3(256), 0, st, p);
         else hipLaunchKernelGGL(gemm_bf16_kernel<AMODE_CONV3>, g, dim3(256), 0, st, p);
-    } else {
-        if (p.gn_part) return -1;                 // GroupNorm partials are a bf16 conv3_halo64_kernel feature
-        p.patch = 0;                              // the exact-mode kernel enumerates pixels linearly
-        // opt-in split-bf16 arithmetic (gemm_split.hip): three bf16 MFMAs per fp32 product where the one predicate holds; every other call is exact fp32 as below
-        if (p.split3 && car_gemm_split_ok(amode, &p)) return car_launch_gemm_split(amode, &p, st) == hipSuccess ? 0 : -2;
-        // exact mode: fp32 MFMA tiles (16 x the VALU rate per CU); the round-1 VALU kernel serves the shapes whose strides break the loader's 16-byte chunks
-        const bool mfma_ok = p.K % 16 == 0 && p.ldw % 4 == 0 && ((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.W & 15) == 0 && p.sA0 % 4 == 0 && p.sA1 % 4 == 0 && p.sW0 % 4 == 0 && p.sW1 % 4 == 0 &&
-                             (amode == AMODE_PLAIN ? p.lda % 4 == 0 : p.Cin % 4 == 0);
-        if (mfma_ok) {
-            dim3 g((p.N + 127) / 128, (p.M + 127) / 128, p.nb0 * p.nb1);
-            if (amode == AMODE_PLAIN) hipLaunchKernelGGL(gemm_f32_mfma_kernel<AMODE_PLAIN>, g, dim3(256), 0, st, p);
-            else if (amode == AMODE_CONV3S2) hipLaunchKernelGGL(gemm_f32_mfma_kernel<AMODE_CONV3S2>, g, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL(gemm_f32_mfma_kernel<AMODE_CONV3>, g, dim3(256), 0, st, p);
-            return 0;
-        }
+        return 0;
+    }
+    case CAR_ROUTE_F32_SPLIT:
+        return car_launch_gemm_split(amode, &p, st) == hipSuccess ? 0 : -2;
+    case CAR_ROUTE_F32_MFMA: {
+        dim3 g((p.N + 127) / 128, (p.M + 127) / 128, p.nb0 * p.nb1);
+        if (amode == AMODE_PLAIN) hipLaunchKernelGGL(gemm_f32_mfma_kernel<AMODE_PLAIN>, g, dim3(256), 0, st, p);
+        else if (amode == AMODE_CONV3S2) hipLaunchKernelGGL(gemm_f32_mfma_kernel<AMODE_CONV3S2>, g, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(gemm_f32_mfma_kernel<AMODE_CONV3>, g, dim3(256), 0, st, p);
+        return 0;
+    }
+    default: {                                    // CAR_ROUTE_F32_VALU
         dim3 g((p.N + 63) / 64, (p.M + 63) / 64, p.nb0 * p.nb1);
         if (amode == AMODE_PLAIN) hipLaunchKernelGGL(gemm_f32_kernel<AMODE_PLAIN>, g, dim3(256), 0, st, p);
         else if (amode == AMODE_CONV3S2) hipLaunchKernelGGL(gemm_f32_kernel<AMODE_CONV3S2>, g, dim3(256), 0, st, p);
         else hipLaunchKernelGGL(gemm_f32_kernel<AMODE_CONV3>, g, dim3(256), 0, st, p);
+        return 0;
     }
-    return 0;
+    }
 }

@@ -56,3 +56,20 @@ def test_nhwc_conv_kernels_against_exact_integer_references():
     out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
     assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
+
+
+def test_generic_gemm_and_conv_kernels_against_exact_integer_references():
+    """gemm.hip (experiments/gemm_check.hip, quick mode, built with -DCAR_DEV_KNOBS so that the CAR_* switches really select the alternate routes): every kernel
+    family behind car_launch_gemm through the real launcher, each case asserting its car_gemm_route value first — gemm_bf16_kernel, gemm_bf16_glds_kernel (tiles == 512
+    exactly, 8 and 9 ring stages, and one batch fewer on the register kernel), conv3_halo64_kernel, conv3_halo_kernel (CAR_CONV_HALO128), gemm_f32_mfma_kernel,
+    gemm_f32_kernel.  Operands are small hashed integers whose products and sums are exact (the harness checks the condition per output element), so the whole output
+    allocation — values, ldc gap columns, batch gaps, guards, all poisoned — is compared with memcmp: plain / batched / 3x3 / stride-2 / folded-upsample gathers over
+    ragged tiles, patch and linear row order, EP_VEC and EP_SCALAR with bias_n / bias_m / scale / residual / alpha, bf16 and fp32 stores, one dense case per
+    epilogue path (EP_VEC, EP_SCALAR, EP_SWIGLU) with sums far beyond 8 bits that replays the documented order of the rounding points, a bias pointer with BIAS_NONE, the GroupNorm partials of the halo epilogue bit-equal to integer sums of the stored
+    values and to gn_partial_vec_kernel's totals, every refusal (gn_part, K % 32 / K % 16) returning its code and writing nothing.  Only the activations and SwiGLU
+    have a bound, derived not measured: one bf16 ulp of the rounded fp64 function (SwiGLU: ulp(gate) |c| + ulp(out)) on at most 1 % of the elements, SiLU over |x| <= 30.5
+    and the GELU forms over [-3.5, 30.5] (below -4.3 their fp32 form cancels).  Two runs, equal bits."""
+    exe = _build("gemm_check", extra=("-DCAR_DEV_KNOBS",))
+    out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
+    assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
