@@ -593,59 +593,56 @@ static void launch_gemm_ij(const GemmDP& p_, int epi, hipStream_t st) {
 #undef LG
 }
 
-// tile shape: I row-blocks x J m-blocks per workgroup, WAVES waves splitting K.  cfg = I*100 + J*10 + (WAVES == 8)
+// tile shape: I row-blocks x J m-blocks per workgroup, WAVES waves splitting K.  cfg = I*100 + J*10 + (WAVES == 8); 112 = one 16-row tile, 16 waves
 // `staged_ok`: the staged on-the-fly norm (NORM == 3) may be chosen where it applies (car_launch_dec_gemm_cfg: always)
-extern "C" int car_launch_dec_gemm_cfg_ex(const GemmDP* p, int epi, int cfg, int staged_ok, hipStream_t st) {
+// The DECISION of the launcher as a pure host function (decode2_params.h DecGemmRoute): 0 and the kernel form that runs, or -1 (refused: nothing is launched).
+// The launcher below only switches on its answer, so a harness that asserts the route of a case cannot disagree with what is launched.
+extern "C" int car_dec_gemm_route(const GemmDP* p, int epi, int cfg, int staged_ok, DecGemmRoute* r) {
+    if (cfg < 100) return -1;
     if (epi == EPI_SWIGLU && cfg < 200) return -1;       // the (a, c) pair needs two adjacent row-blocks in one tile
     if (p->N % (16 * (cfg / 100)) || p->K % 32) return -1;
     if (p->wscale && p->K % 64) return -1;
     const int f8 = p->wscale ? (p->f8_mfma ? 2 : 1) : 0;
+    const int I = cfg / 100, J = (cfg / 10) % 10, w8 = cfg % 10;
+    const bool ij_ok = (I == 1 || I == 2 || I == 4) && (J == 1 || J == 2 || J == 4) && w8 <= 1 && cfg < 500;
+    r->I = I; r->J = J; r->WAVES = w8 ? 8 : 4; r->F8 = f8; r->NORM = 0;
     if (p->ssq_in) {                                     // normalise-on-the-fly variant (NORM == 2): any tile; X = the bf16 residual rows themselves
         if (!p->nw || !p->nh_in || epi == EPI_RESID || p->ssq_np <= 0 || (p->ssq_np & 3) || p->ssq_np > 128) return -1;
+        if (!ij_ok) return -1;
         // one m-block, 8-wave tiles: the staged form (NORM == 3) — same arithmetic, lane-dense operand loads.  Limits: a slice of at most 16 k-blocks per wave
         // (one DMA instruction for the norm weight) and at least one k-unit for every wave.
-        {
-            const int nku = p->K / (f8 ? 64 : 32), nkw_max = (nku + 7) / 8;
-            if (p->M <= 16 && (cfg / 10) % 10 == 1 && cfg % 10 == 1 && nku >= 8 && nkw_max * (f8 ? 2 : 1) <= 16 && staged_ok) {
-                switch (cfg / 100) {
-#define CASE3(I) case I: if (f8 == 2) launch_gemm_ij<I, 1, 8, 2, 3>(*p, epi, st); else if (f8) launch_gemm_ij<I, 1, 8, 1, 3>(*p, epi, st); else launch_gemm_ij<I, 1, 8, 0, 3>(*p, epi, st); return 0;
-                    CASE3(1) CASE3(2) CASE3(4)
-#undef CASE3
-                    default: break;
-                }
-            }
-        }
-        switch (cfg) {
-#define CASE(I, J) case I * 100 + J * 10: if (f8 == 2) launch_gemm_ij<I, J, 4, 2, 2>(*p, epi, st); else if (f8) launch_gemm_ij<I, J, 4, 1, 2>(*p, epi, st); else launch_gemm_ij<I, J, 4, 0, 2>(*p, epi, st); break; \
-                   case I * 100 + J * 10 + 1: if (f8 == 2) launch_gemm_ij<I, J, 8, 2, 2>(*p, epi, st); else if (f8) launch_gemm_ij<I, J, 8, 1, 2>(*p, epi, st); else launch_gemm_ij<I, J, 8, 0, 2>(*p, epi, st); break;
-            CASE(1, 1) CASE(1, 2) CASE(1, 4) CASE(2, 1) CASE(2, 2) CASE(2, 4) CASE(4, 1) CASE(4, 2) CASE(4, 4)
-#undef CASE
-            default: return -1;
-        }
+        const int nku = p->K / (f8 ? 64 : 32), nkw_max = (nku + 7) / 8;
+        r->NORM = (p->M <= 16 && J == 1 && w8 == 1 && nku >= 8 && nkw_max * (f8 ? 2 : 1) <= 16 && staged_ok) ? 3 : 2;
         return 0;
     }
     if (p->nw) {                                         // fused-norm variant: one m-block
-        if (p->M > 16 || (cfg / 10) % 10 != 1 || epi == EPI_RESID || p->K > 2048) return -1;
-        switch (cfg) {
-#define CASE(I) case I * 100 + 10: if (f8 == 2) launch_gemm_ij<I, 1, 4, 2, 1>(*p, epi, st); else if (f8) launch_gemm_ij<I, 1, 4, 1, 1>(*p, epi, st); else launch_gemm_ij<I, 1, 4, 0, 1>(*p, epi, st); break; \
-                case I * 100 + 11: if (f8 == 2) launch_gemm_ij<I, 1, 8, 2, 1>(*p, epi, st); else if (f8) launch_gemm_ij<I, 1, 8, 1, 1>(*p, epi, st); else launch_gemm_ij<I, 1, 8, 0, 1>(*p, epi, st); break;
-            CASE(1) CASE(2) CASE(4)
-#undef CASE
-            default: return -1;
-        }
+        if (p->M > 16 || J != 1 || epi == EPI_RESID || p->K > 2048) return -1;
+        if (!ij_ok) return -1;
+        r->NORM = 1;
         return 0;
     }
-    switch (cfg) {
-#define CASE(I, J) case I * 100 + J * 10: if (f8 == 2) launch_gemm_ij<I, J, 4, 2, 0>(*p, epi, st); else if (f8) launch_gemm_ij<I, J, 4, 1, 0>(*p, epi, st); else launch_gemm_ij<I, J, 4, 0, 0>(*p, epi, st); break; \
-                   case I * 100 + J * 10 + 1: if (f8 == 2) launch_gemm_ij<I, J, 8, 2, 0>(*p, epi, st); else if (f8) launch_gemm_ij<I, J, 8, 1, 0>(*p, epi, st); else launch_gemm_ij<I, J, 8, 0, 0>(*p, epi, st); break;
-        CASE(1, 1) CASE(1, 2) CASE(1, 4) CASE(2, 1) CASE(2, 2) CASE(2, 4) CASE(4, 1) CASE(4, 2) CASE(4, 4)
-#undef CASE
-        // 16 waves per 16-row tile (round 6): the narrow linears of a small chain (wo, w2: N / 16 = 80 workgroups) are bound by what one CU pulls; 16 waves keep
-        // twice the bytes in flight per CU
-        case 112: if (f8 == 2) launch_gemm_ij<1, 1, 16, 2, 0>(*p, epi, st); else if (f8) launch_gemm_ij<1, 1, 16, 1, 0>(*p, epi, st); else launch_gemm_ij<1, 1, 16, 0, 0>(*p, epi, st); break;
+    // 16 waves per 16-row tile (round 6): the narrow linears of a small chain (wo, w2: N / 16 = 80 workgroups) are bound by what one CU pulls; 16 waves keep
+    // twice the bytes in flight per CU
+    if (cfg == 112) { r->I = 1; r->J = 1; r->WAVES = 16; return 0; }
+    return ij_ok ? 0 : -1;
+}
+
+extern "C" int car_launch_dec_gemm_cfg_ex(const GemmDP* p, int epi, int cfg, int staged_ok, hipStream_t st) {
+    DecGemmRoute r;
+    if (car_dec_gemm_route(p, epi, cfg, staged_ok, &r)) return -1;
+#define RT(NM, I, J, W) case NM * 100000 + I * 1000 + J * 100 + W: if (r.F8 == 2) launch_gemm_ij<I, J, W, 2, NM>(*p, epi, st); else if (r.F8) launch_gemm_ij<I, J, W, 1, NM>(*p, epi, st); else launch_gemm_ij<I, J, W, 0, NM>(*p, epi, st); return 0;
+#define RT2(NM, I, J) RT(NM, I, J, 4) RT(NM, I, J, 8)
+#define RT9(NM) RT2(NM, 1, 1) RT2(NM, 1, 2) RT2(NM, 1, 4) RT2(NM, 2, 1) RT2(NM, 2, 2) RT2(NM, 2, 4) RT2(NM, 4, 1) RT2(NM, 4, 2) RT2(NM, 4, 4)
+    switch (r.NORM * 100000 + r.I * 1000 + r.J * 100 + r.WAVES) {
+        RT9(0) RT(0, 1, 1, 16)
+        RT2(1, 1, 1) RT2(1, 2, 1) RT2(1, 4, 1)
+        RT9(2)
+        RT(3, 1, 1, 8) RT(3, 2, 1, 8) RT(3, 4, 1, 8)
         default: return -1;
     }
-    return 0;
+#undef RT9
+#undef RT2
+#undef RT
 }
 
 extern "C" int car_launch_dec_gemm_cfg(const GemmDP* p, int epi, int cfg, hipStream_t st) { return car_launch_dec_gemm_cfg_ex(p, epi, cfg, 1, st); }

@@ -65,6 +65,11 @@ struct GemmDP {
     CAR_STAMP_FIELDS
 };
 
+// What car_launch_dec_gemm_cfg_ex runs for (descriptor, epilogue, cfg): car_dec_gemm_route returns 0 and fills this, or -1 for a refused call (nothing launched).
+// NORM: 0 packed X, 1 prologue norm, 2 on-the-fly norm from ssq_in, 3 its staged (LDS-DMA) form.  F8: 0 bf16 weights, 1 e4m3 weights widened, 2 W8A8.
+struct DecGemmRoute { int I, J, WAVES, F8, NORM; };
+extern "C" int car_dec_gemm_route(const GemmDP* p, int epi, int cfg, int staged_ok, DecGemmRoute* r);
+
 // =============================================================================================== attention
 // Edge blocks of dec_attn2_kernel (bf16 cache): which lanes of the eight 1-KiB loads of a 32-position block hold a row the sequence attends.  [lo, hi] is the
 // attended range inside the block (0 <= lo, hi <= 31; empty if lo > hi).  A lane that holds none is not loaded (it gets zeros: its scores are masked to -inf and

@@ -73,3 +73,28 @@ def test_generic_gemm_and_conv_kernels_against_exact_integer_references():
     out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
     assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
+
+
+def test_bf16_decode_kernels_against_exact_integer_references():
+    """decode2.hip (experiments/decode_check.hip, quick mode): dec_gemm_kernel, rmsnorm2_kernel and the two writers of the packed KV cache (the EPI_QKV epilogue,
+    prefill_rope_kv2_kernel) through the real launchers, every dec_gemm case asserting its car_dec_gemm_route value (I, J, WAVES, F8, NORM) first.  Operands are
+    small hashed integers (times a power of two), wscale rows powers of two, RoPE tables dyadic pairs: every partial sum is exact in fp32 (checked per output
+    element, the sums of squares behind ssq_out included), so the reference — the documented bf16 / e4m3 rounding points replayed on exact sums — has one possible
+    result, and the WHOLE poisoned arena of a case is compared with memcmp: outputs, inputs, guards, cache rows at positions other than *pos, rows >= M of the packed
+    SwiGLU output, of ssq_out, h, outf and qout; rows >= M of a packed X hold NaNs.  Every tile shape (18 + the 16-wave one) x every epilogue x bf16 / e4m3 / W8A8
+    weights (ties 17 -> 16, 19 -> 20 and values beyond 448 in the activations and in the e4m3 KV rows); M in {1, 2, 5, 16, 17, 50, 70}; K below the wave count,
+    unevenly split, and deep enough for the refill branch to run more than once; grids with the XCD remap on and off; helper workgroups; both w_nt bits; EPI_RESID
+    with and without ssq_out; EPI_QKV at positions 0 / 15 / 16 / 31 / 32 / 33 / SA - 1 with the prologue and the late read of *pos; every refusal returns non-zero and
+    writes nothing.  Norm forms on sign rows +-2^a(m) (rnd(v rstd) = +-1 for every rstd within 2 ulp, so no tolerance): rmsnorm2 -> packed xn -> NORM 0 for
+    D = 256 .. 4096, NORM 1 with gather / control add / nh_out, NORM 2 on every tile and NORM 3 for K = 256 / 768 / 1280, their partials written by a preceding
+    EPI_RESID launch.  Integer rows in [-8, 8]: every rmsnorm2 row equals the row of ONE of the three candidate rstd values (the correctly rounded 1/sqrt and its
+    neighbours: rsqrtf's documented 1 ulp), and NORM 1 / 2 / 3 are bit-equal to rmsnorm2 followed by NORM 0 of the same tile shape.  The prefill writer for Tn in
+    {1, 33, 40} x t0 in {0, 7, 32}, and a decode-time row that must land behind it.  One-hot attention (H = 2, SA = 96, T = 40, b in {1, 8, 17}): q = 16 e_d and
+    K_p[d] = 8 make one attended position win by >= 128, every other probability is exactly 0 and the output must be the bits of V_p — bf16 and e4m3 caches under
+    every variant, dec_attn2s (162) with and without helpers, the persistent grid, packed output, nsplit 1 / 4, masks with holes through the in-kernel scan; masked
+    and never-written rows hold +-3e38 / +-448.  The only bound is SwiGLU's, derived in gemm_check.hip: ulp(gate) |c| + ulp(out) from the rounded fp64 function on
+    at most 1 % of the elements."""
+    exe = _build("decode_check")
+    out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
+    assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
