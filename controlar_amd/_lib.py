@@ -45,6 +45,16 @@ class CarT5Config(C.Structure):
     ]
 
 
+class CarClipConfig(C.Structure):
+    _fields_ = [
+        ("vision_width", C.c_int32), ("vision_layers", C.c_int32), ("vision_heads", C.c_int32), ("vision_mlp", C.c_int32),
+        ("image_size", C.c_int32), ("patch", C.c_int32),
+        ("text_width", C.c_int32), ("text_layers", C.c_int32), ("text_heads", C.c_int32), ("text_mlp", C.c_int32),
+        ("vocab_size", C.c_int32), ("context_length", C.c_int32), ("proj_dim", C.c_int32), ("ln_eps", C.c_float),
+        ("reserved", C.c_int32 * 10),
+    ]
+
+
 class CarDptConfig(C.Structure):
     _fields_ = [
         ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("mlp", C.c_int32), ("pos_grid", C.c_int32),
@@ -82,6 +92,11 @@ SYMBOLS = {
     "car_import_packed": (C.c_int, [C.c_void_p, C.c_char_p]),
     "car_t5_configure": (C.c_int, [C.c_void_p, C.POINTER(CarT5Config)]),
     "car_t5_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "car_clip_configure": (C.c_int, [C.c_void_p, C.POINTER(CarClipConfig)]),
+    "car_clip_encode_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_clip_encode_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "car_clip_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_debug_clip_requant_table": (C.c_int, [C.c_void_p]),
     "car_encode_control": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "car_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                C.POINTER(CarSampling), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -122,6 +122,51 @@ def small_t5() -> T5Config:
 
 
 @dataclass
+class CLIPConfig:
+    """HF CLIPConfig fields both towers read (evaluations/t2i/evaluation.py:129-176 loads OpenAI's ViT-B/32).  Heads are 64 wide in both towers."""
+    vision_width: int = 768
+    vision_layers: int = 12
+    vision_heads: int = 12
+    vision_mlp: int = 3072
+    image_size: int = 224
+    patch: int = 32
+    text_width: int = 512
+    text_layers: int = 12
+    text_heads: int = 8
+    text_mlp: int = 2048
+    vocab_size: int = 49408
+    context_length: int = 77
+    proj_dim: int = 512
+    ln_eps: float = 1e-5
+
+    @property
+    def eot_id(self) -> int:
+        """The end-of-text id of OpenAI's BPE vocabulary layout: the last id, hence the largest (49407 at full size)."""
+        return self.vocab_size - 1
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch
+
+
+def clip_vit_b32() -> CLIPConfig:
+    """OpenAI CLIP ViT-B/32, the model compute_clip_score loads."""
+    return CLIPConfig()
+
+
+def tiny_clip() -> CLIPConfig:
+    """2 x 2 patches plus the class row, 2 heads, 2 layers, the full 77-token context."""
+    return CLIPConfig(vision_width=128, vision_layers=2, vision_heads=2, vision_mlp=256, image_size=32, patch=16,
+                      text_width=128, text_layers=2, text_heads=2, text_mlp=256, vocab_size=512, context_length=77, proj_dim=64)
+
+
+def small_clip() -> CLIPConfig:
+    """ViT-B/32's token grid (7 x 7 + 1 = 50 vision rows) at a quarter of its width."""
+    return CLIPConfig(vision_width=256, vision_layers=3, vision_heads=4, vision_mlp=512, image_size=224, patch=32,
+                      text_width=128, text_layers=3, text_heads=2, text_mlp=256, vocab_size=1024, context_length=77, proj_dim=128)
+
+
+@dataclass
 class DPTConfig:
     """HF DPTConfig fields that DPTForDepthEstimation reads (sample_t2i.py:33,114-116 loads Intel/dpt-large).  The library runs the shipped family only:
     the fields below the blank line are fixed, and ``Engine.load_depth`` refuses any other value at configure time."""

@@ -98,8 +98,9 @@ __device__ inline float gelu_tanh_f(float x) {
     return 0.5f * x * (1.0f + tanhf(k * (x + 0.044715f * x * x * x)));
 }
 __device__ inline float silu_f(float x) { return x / (1.0f + expf(-x)); }
+__device__ inline float quick_gelu_f(float x) { return x / (1.0f + expf(-1.702f * x)); }   // CLIP's x * sigmoid(1.702 x)
 
-enum { ACT_NONE = 0, ACT_GELU_ERF = 1, ACT_GELU_TANH = 2, ACT_SILU = 3 };
+enum { ACT_NONE = 0, ACT_GELU_ERF = 1, ACT_GELU_TANH = 2, ACT_SILU = 3, ACT_QUICK_GELU = 4 };
 enum { BIAS_NONE = 0, BIAS_N = 1, BIAS_M = 2 };
 enum { AMODE_PLAIN = 0, AMODE_CONV3 = 1, AMODE_CONV3S2 = 2 };
 // what car_gemm_route (gemm.hip) answers: the kernel family a descriptor takes through car_launch_gemm, or (negative) why the launcher refuses it

@@ -45,6 +45,13 @@ void car_launch_t5_softmax(int mode, const float* S, long lds, void* P, long ldp
                            const unsigned char* mask, int Tq, int n_head, hipStream_t st);
 void car_launch_t5_gated_act(int mode, const void* in, void* out, long rows, int hidden, hipStream_t st);
 int car_launch_flash64(const FlashP* p, int B, hipStream_t st);
+// clip.hip
+void car_launch_clip_requant(const unsigned char* src, unsigned char* dst, const unsigned char* host_table, long n, hipStream_t st);
+void car_launch_clip_pixels_to_patches(int mode, const ClipPatchP* p, hipStream_t st);
+void car_launch_clip_text_embed(int mode, const long long* ids, const void* tok, const void* pos, void* h, long B, int T, int D, int vocab, int* err_flag, hipStream_t st);
+void car_launch_clip_pool(int mode, const void* h, const long long* ids, void* out, int B, int T, int D, int vocab, hipStream_t st);
+void car_launch_clip_cosine(const float* a, const float* b, int B, int D, float eps, float* out, hipStream_t st);
+void car_launch_clip_mean(const float* v, int n, double* out, hipStream_t st);
 int car_launch_gemm(int mode, int amode, const GemmP* p, hipStream_t st);   // -1: GemmP::gn_part on a call that cannot take conv3_halo64_kernel; -3: K no multiple of the kernels' step (bf16 32, fp32 16) — nothing launched (car_gemm_route)
 int car_conv3_halo64_ok(int mode, const GemmP* p);
 void car_launch_convert(int mode, const void* src, int src_dtype, void* dst, long n, hipStream_t st);
@@ -144,7 +151,7 @@ struct car_ctx {
     int n_cu = 256;       // compute units of the device (persistent-grid sizing)
     DevBuf rowimg;       // [b] int: image index of each row
     DevBuf rowunc; std::vector<int> h_rowunc;   // c2i: uncond-row marks (device + the host copy the async upload reads)
-    int* host_flags = nullptr;   // sticky error flags raised by device code, in host-mapped pinned memory ([0] = class label out of range, [1] = first_valid_hint too large, [2] = car_score token id out of range): the kernel writes it
+    int* host_flags = nullptr;   // sticky error flags raised by device code, in host-mapped pinned memory ([0] = class label out of range, [1] = first_valid_hint too large, [2] = car_score token id out of range, [3] = car_clip_encode_text token id out of range): the kernel writes it
                                  // with a system-scope store, and every entry that takes this context reads it without a host wait (check_sticky)
     DevBuf canny_map;    // car_canny: uint8 [B,H,W] candidate/edge map + the "changed" flag
     DevBuf lineart_ws;   // car_lineart: NHWC activations, raw fp32 conv outputs and InstanceNorm partials of one chunk of images (grows on demand)
@@ -159,6 +166,9 @@ struct car_ctx {
     car_t5_config t5 = {}; bool has_t5 = false;
     DevBuf t5_in;        // int32 ids [B*T] | uint8 key mask [B*T] | staging for host-side int64 inputs
     DevBuf t5_bias; int t5_bias_T = 0;   // position bias fp32 [heads][T][T] of the last sequence length
+    car_clip_config clip = {}; bool has_clip = false;   // car_clip_configure
+    DevBuf clip_u8;      // car_clip_encode_image: the requantised copy of one chunk of the input and its bicubic-resized image (uint8)
+    DevBuf clip_ones;    // car_clip_encode_text: the all-ones key mask [chunk][T] of the causal attention
     int st_b = 0, st_T = 0, st_nsteps = 0, st_has_mask = 0; double st_wbytes = 0; const int* st_jmin = nullptr;   // inputs of the lazy decode_algo_bytes
     // decode graph
     hipGraphExec_t gexec = nullptr; std::string gkey;          // the captured decode step(s): `graph_steps` consecutive tokens per replay
@@ -178,6 +188,7 @@ static inline int check_sticky(car_ctx* c) {
     volatile int* f = c->host_flags;
     if (f[1]) { f[1] = 0; FAIL(c, "car_generate: an earlier call passed a first_valid_hint beyond the first valid prompt position of its batch: valid prompt rows were left out of the prefill, its tokens are invalid"); }
     if (f[2]) { f[2] = 0; FAIL(c, "car_score: an earlier call on this context received a token id outside [0, %d) (read as token 0 on the device): its results are invalid", c->cfg.vocab_size); }
+    if (f[3]) { f[3] = 0; FAIL(c, "car_clip_encode_text: an earlier call on this context received a token id outside [0, %d) (read as token 0 on the device): its embeddings are invalid", c->clip.vocab_size); }
     if (f[0]) { f[0] = 0; FAIL(c, "car_generate_c2i: an earlier call on this context received a class label outside [0, %d] (clamped to the null class on the device): its tokens are invalid", c->cfg.num_classes); }
     return 0;
 }
@@ -271,18 +282,20 @@ struct LoadedTensor {
     int ndim() const { return (int)shape.size(); }
 };
 // Every model family keeps its loader and the list of tensors car_finalize_weights asks for next to its runner: engine_lineart.hip ("lineart."),
-// engine_hed.hip ("hed."), engine_depth.hip ("depth."), engine_t5.hip ("t5."), engine_vq.hip (decoder. / encoder. / quant* / post_quant_conv.),
+// engine_hed.hip ("hed."), engine_depth.hip ("depth."), engine_t5.hip ("t5."), engine_clip.hip ("clip."), engine_vq.hip (decoder. / encoder. / quant* / post_quant_conv.),
 // engine_weights.hip (the GPT and its ViT adapter).  A name list holds what the loaders leave in car_ctx::w (host_keep for the DPT position table).
 int lineart_load_tensor(car_ctx* c, const LoadedTensor& t);
 int hed_load_tensor(car_ctx* c, const LoadedTensor& t);
 int depth_load_tensor(car_ctx* c, const LoadedTensor& t);
 int t5_load_tensor(car_ctx* c, const LoadedTensor& t);
+int clip_load_tensor(car_ctx* c, const LoadedTensor& t);
 int vq_load_tensor(car_ctx* c, const LoadedTensor& t);
 int gpt_load_tensor(car_ctx* c, const LoadedTensor& t);
 void lineart_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void hed_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void depth_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void t5_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+void clip_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void vq_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void gpt_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 // engine_weights.hip

@@ -77,6 +77,7 @@ __device__ __forceinline__ void store_strip(const GemmP& p, const float* strip, 
                     if (p.act == ACT_GELU_ERF) x = bf2f(f2bf(gelu_erf_f(x)));
                     else if (p.act == ACT_GELU_TANH) x = bf2f(f2bf(gelu_tanh_f(x)));
                     else if (p.act == ACT_SILU) x = bf2f(f2bf(silu_f(x)));
+                    else if (p.act == ACT_QUICK_GELU) x = bf2f(f2bf(quick_gelu_f(x)));
                     if (scale) x = bf2f(f2bf(x * sv[e]));
                     if (R) x = bf2f(f2bf(x + rv8[e]));
                     v[e] = x;

@@ -12,6 +12,7 @@ __device__ __forceinline__ float epi_value(const GemmP& p, const T* bias, const 
     if (p.act == ACT_GELU_ERF) v = ET<T>::rnd(gelu_erf_f(v));
     else if (p.act == ACT_GELU_TANH) v = ET<T>::rnd(gelu_tanh_f(v));
     else if (p.act == ACT_SILU) v = ET<T>::rnd(silu_f(v));
+    else if (p.act == ACT_QUICK_GELU) v = ET<T>::rnd(quick_gelu_f(v));
     if (scale) v = ET<T>::rnd(v * ET<T>::ld(scale + n));
     if (R) v = ET<T>::rnd(v + ET<T>::ld(R + zR + mrow * p.ldr + n));
     return v;

@@ -127,3 +127,14 @@ struct ResampleP {
     unsigned char* tmp; long tmp_img; int tmp_pitch;
     unsigned char* out; void* control; float* fout; int norm, Wo, final;
 };
+
+// ------------------------------------------------------------------ CLIP score (clip.hip; evaluations/t2i/evaluation.py:129-176)
+// clip_pixels_to_patches: the tail of CLIP's preprocessor on the uint8 [B][Hr][Wr][3] output of the bicubic resize.  Pixel (y, x) of the n_px x n_px
+// centre crop is source pixel (top + y, left + x); its value is v = ((u / 255) - mean[c]) / std[c], every step rounded to fp32 once (correctly rounded
+// divisions, no contraction).  v goes to patches[(b*g*g + (y/patch)*g + x/patch)][c*patch*patch + (y%patch)*patch + x%patch] (row pitch Kp, the columns
+// [3*patch*patch, Kp) written as 0) in the element type, and to pixel_values [B][3][n_px][n_px] fp32 when that is given.
+struct ClipPatchP {
+    const unsigned char* src; void* patches; float* pixel_values;
+    int B, Hr, Wr, top, left, n_px, patch, g, Kp;
+    float mean[3], std[3];
+};

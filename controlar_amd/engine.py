@@ -565,6 +565,73 @@ class Engine:
                                            C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())), "car_t5_encode")
         return out
 
+    # ------------------------------------------------------------------ CLIP score (evaluations/t2i/evaluation.py:129-176)
+    def clip_configure(self, ccfg):
+        """car_clip_configure from a config.CLIPConfig."""
+        cc = L.CarClipConfig()
+        cc.vision_width, cc.vision_layers, cc.vision_heads, cc.vision_mlp = ccfg.vision_width, ccfg.vision_layers, ccfg.vision_heads, ccfg.vision_mlp
+        cc.image_size, cc.patch = ccfg.image_size, ccfg.patch
+        cc.text_width, cc.text_layers, cc.text_heads, cc.text_mlp = ccfg.text_width, ccfg.text_layers, ccfg.text_heads, ccfg.text_mlp
+        cc.vocab_size, cc.context_length, cc.proj_dim, cc.ln_eps = ccfg.vocab_size, ccfg.context_length, ccfg.proj_dim, ccfg.ln_eps
+        self._check(self.lib.car_clip_configure(self._h, C.byref(cc)), "car_clip_configure")
+        self.clipcfg = ccfg
+
+    def load_clip_state_dict(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
+        """HF CLIPModel state-dict names; the C ABI namespaces them under 'clip.'."""
+        self.load_state_dict({"clip." + k: v for k, v in sd.items()}, finalize=finalize)
+
+    def _clip_proj(self) -> int:
+        ccfg = getattr(self, "clipcfg", None)
+        return ccfg.proj_dim if ccfg is not None else 1          # not configured: the library refuses the call and says why
+
+    def clip_encode_image(self, img: torch.Tensor, requant: bool = False, want_pixel_values: bool = False, want_embedding: bool = True):
+        """CLIP's preprocessor and image tower on the GPU (car_clip_encode_image).  img uint8 [B,H,W,3] (or [H,W,3]); requant: the evaluation script's
+        ToTensor / Normalize(0.5) / tensor2pil round trip first.  Returns fp32 [B,proj_dim]; with want_pixel_values also fp32 [B,3,n_px,n_px]."""
+        if img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3 or img.numel() == 0:
+            raise ValueError(f"clip_encode_image: expected a non-empty uint8 image [B,H,W,3] or [H,W,3], got {img.dtype} {tuple(img.shape)}")
+        x = (img[None] if img.dim() == 3 else img).to(self.device).contiguous()
+        B, H, W, _ = x.shape
+        n = self.clipcfg.image_size if getattr(self, "clipcfg", None) is not None else 1
+        emb = torch.empty(B, self._clip_proj(), dtype=torch.float32, device=self.device) if want_embedding else None
+        pv = torch.empty(B, 3, n, n, dtype=torch.float32, device=self.device) if want_pixel_values else None
+        self._check(self.lib.car_clip_encode_image(self._h, C.c_void_p(x.data_ptr()), B, H, W, int(bool(requant)),
+                                                   C.c_void_p(emb.data_ptr() if emb is not None else 0), C.c_void_p(pv.data_ptr() if pv is not None else 0),
+                                                   C.c_void_p(_stream_ptr())), "car_clip_encode_image")
+        out = tuple(t for t in (emb, pv) if t is not None)
+        return out[0] if len(out) == 1 else out
+
+    def clip_encode_text(self, ids: torch.Tensor) -> torch.Tensor:
+        """CLIP's text tower on the GPU (car_clip_encode_text).  ids integer [B,T], T <= context_length -> fp32 [B,proj_dim].  An id outside [0, vocab) on
+        a host tensor raises here; on a device tensor it raises the sticky flag (check_errors)."""
+        if not torch.is_tensor(ids) or ids.dim() != 2 or ids.dtype.is_floating_point or ids.numel() == 0:
+            raise ValueError(f"clip_encode_text: expected non-empty integer ids [B,T], got {tuple(getattr(ids, 'shape', ()))}")
+        proj = self._clip_proj()
+        if ids.device.type == "cpu" and getattr(self, "clipcfg", None) is not None:
+            lo, hi = int(ids.min()), int(ids.max())
+            if lo < 0 or hi >= self.clipcfg.vocab_size:
+                raise RuntimeError(f"car_clip_encode_text: token id out of range [0,{self.clipcfg.vocab_size}) (got {lo}..{hi})")
+        x = ids.to(device=self.device, dtype=torch.int64).contiguous()
+        B, T = x.shape
+        emb = torch.empty(B, proj, dtype=torch.float32, device=self.device)
+        self._check(self.lib.car_clip_encode_text(self._h, C.c_void_p(x.data_ptr()), B, T, C.c_void_p(emb.data_ptr()), C.c_void_p(_stream_ptr())),
+                    "car_clip_encode_text")
+        return emb
+
+    def clip_score(self, img_emb: torch.Tensor, txt_emb: torch.Tensor, n_mean: Optional[int] = None):
+        """F.cosine_similarity(img_emb, txt_emb, dim=1) on the GPU (car_clip_score): fp32 [B]; with n_mean also the fp64 mean of the first n_mean values
+        as a 0-dim device tensor."""
+        proj = self._clip_proj()
+        a = img_emb.to(device=self.device, dtype=torch.float32).contiguous()
+        b = txt_emb.to(device=self.device, dtype=torch.float32).contiguous()
+        if a.dim() != 2 or a.shape != b.shape or a.shape[1] != proj or a.shape[0] == 0:
+            raise ValueError(f"clip_score: expected two [B,{proj}] tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+        B = a.shape[0]
+        out = torch.empty(B, dtype=torch.float32, device=self.device)
+        mean = torch.empty(1, dtype=torch.float64, device=self.device) if n_mean is not None else None
+        self._check(self.lib.car_clip_score(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), B, int(n_mean or 0), C.c_void_p(out.data_ptr()),
+                                            C.c_void_p(mean.data_ptr() if mean is not None else 0), C.c_void_p(_stream_ptr())), "car_clip_score")
+        return (out, mean[0]) if mean is not None else out
+
     def check_errors(self):
         """Waits for the work enqueued on this context and raises if device code reported an error no entry could fail on synchronously
         (today: a c2i class label outside [0, num_classes] in a device-resident label tensor — include/controlar_hip.h, car_generate_c2i)."""

@@ -148,3 +148,34 @@ class ControlConsistency:
         else:
             vals = e.rmse(got, want, scale_to_max=True)
         return vals, vals.mean()
+
+
+class CLIPScore:
+    """Prompt alignment as ``compute_clip_score`` reports it (evaluations/t2i/evaluation.py:129-176): the cosine between CLIP's image and text
+    embeddings of every pair, and the mean over the first ``how_many`` pairs in the order they came, which is where the script cuts.  ``scorer``: a
+    ``clip.CLIPScorer`` (its weights loaded).  ``update(pixels, ids)``: ``pixels`` [B,3,H,W] in [-1,1] straight from ``vq_decode``, ``ids`` [B,T] as
+    ``clip.photo_depicts_ids`` leaves them; returns the batch's fp32 cosines.  Everything stays on the device until ``calculate()``."""
+
+    def __init__(self, scorer, how_many: int = 5000, eval_res: int = 256):
+        if how_many < 1:
+            raise ValueError(f"how_many must be at least 1, got {how_many}")
+        self.scorer = scorer
+        self.how_many = int(how_many)
+        self.eval_res = int(eval_res)
+        self._values = []
+
+    def update(self, pixels: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+        vals = self.scorer.score(pixels, ids, eval_res=self.eval_res)
+        self._values.append(vals)
+        return vals
+
+    @property
+    def per_image(self) -> torch.Tensor:
+        """Every pair's cosine so far, fp32, in the order of the updates."""
+        return torch.cat(self._values) if self._values else torch.empty(0, dtype=torch.float32, device=self.scorer.device)
+
+    def calculate(self) -> float:
+        vals = self.per_image
+        if vals.numel() == 0:
+            raise ValueError("No images have been added.")
+        return float(vals[:self.how_many].to(torch.float64).mean())          # one scalar leaves the device: the script's torch.cat(...)[:how_many].mean()

@@ -15,7 +15,7 @@ from typing import Dict
 
 import torch
 
-from .config import PathConfig, GPTConfig, ViTConfig, VQConfig, T5Config, DPTConfig
+from .config import PathConfig, GPTConfig, ViTConfig, VQConfig, T5Config, DPTConfig, CLIPConfig
 
 
 class _Rng:
@@ -348,6 +348,78 @@ def t5_tokens(batch: int, cfg: T5Config, seed: int = 4321, lengths=None):
         ids[b, L - 1] = 1
         mask[b, :L] = 1
     return ids, mask
+
+
+def clip_state_dict(cfg: CLIPConfig, seed: int = 17) -> Dict[str, torch.Tensor]:
+    """HF CLIPModel.state_dict() names and shapes (text_model.*, vision_model.*, visual_projection.weight, text_projection.weight, logit_scale).
+    Linears are fan-in scaled so activations stay O(1) through the layers; biases, the class token, positions and the norm offsets are large enough
+    that dropping any of them shows."""
+    r = _Rng(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def tower(p, D, F, layers):
+        for i in range(layers):
+            q = f"{p}encoder.layers.{i}."
+            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                sd[q + f"self_attn.{n}.weight"] = r.normal(D, D, std=(1.5 if n in ("q_proj", "k_proj") else 1.0) * D ** -0.5)
+                sd[q + f"self_attn.{n}.bias"] = r.normal(D, std=0.05)
+            sd[q + "layer_norm1.weight"] = 1.0 + 0.1 * r.normal(D)
+            sd[q + "layer_norm1.bias"] = r.normal(D, std=0.05)
+            sd[q + "mlp.fc1.weight"] = r.normal(F, D, std=D ** -0.5)
+            sd[q + "mlp.fc1.bias"] = r.normal(F, std=0.05)
+            sd[q + "mlp.fc2.weight"] = r.normal(D, F, std=F ** -0.5)
+            sd[q + "mlp.fc2.bias"] = r.normal(D, std=0.05)
+            sd[q + "layer_norm2.weight"] = 1.0 + 0.1 * r.normal(D)
+            sd[q + "layer_norm2.bias"] = r.normal(D, std=0.05)
+
+    Dt, Dv, g = cfg.text_width, cfg.vision_width, cfg.grid
+    sd["logit_scale"] = torch.tensor(math.log(1 / 0.07), dtype=torch.float32)
+    sd["text_model.embeddings.token_embedding.weight"] = r.normal(cfg.vocab_size, Dt, std=0.5)
+    sd["text_model.embeddings.position_embedding.weight"] = r.normal(cfg.context_length, Dt, std=0.3)
+    tower("text_model.", Dt, cfg.text_mlp, cfg.text_layers)
+    sd["text_model.final_layer_norm.weight"] = 1.0 + 0.1 * r.normal(Dt)
+    sd["text_model.final_layer_norm.bias"] = r.normal(Dt, std=0.05)
+    sd["vision_model.embeddings.class_embedding"] = r.normal(Dv, std=0.5)
+    sd["vision_model.embeddings.patch_embedding.weight"] = r.normal(Dv, 3, cfg.patch, cfg.patch, std=(3 * cfg.patch * cfg.patch) ** -0.5)
+    sd["vision_model.embeddings.position_embedding.weight"] = r.normal(g * g + 1, Dv, std=0.3)
+    sd["vision_model.pre_layrnorm.weight"] = 1.0 + 0.1 * r.normal(Dv)
+    sd["vision_model.pre_layrnorm.bias"] = r.normal(Dv, std=0.05)
+    tower("vision_model.", Dv, cfg.vision_mlp, cfg.vision_layers)
+    sd["vision_model.post_layernorm.weight"] = 1.0 + 0.1 * r.normal(Dv)
+    sd["vision_model.post_layernorm.bias"] = r.normal(Dv, std=0.05)
+    sd["visual_projection.weight"] = r.normal(cfg.proj_dim, Dv, std=Dv ** -0.5)
+    sd["text_projection.weight"] = r.normal(cfg.proj_dim, Dt, std=Dt ** -0.5)
+    return sd
+
+
+def clip_tokens(batch: int, cfg: CLIPConfig, lengths=None, seed: int = 977) -> torch.Tensor:
+    """Tokenizer-shaped ids int64 [batch, context_length] as OpenAI's ``clip.tokenize`` lays them out: the start token (eot - 1), caption ids below it,
+    ONE end-of-text id (``cfg.eot_id``, the largest) at ``lengths[i] - 1``, zeros after it.  ``lengths[i]`` >= 2 (start + end)."""
+    T, eot = cfg.context_length, cfg.eot_id
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.zeros(batch, T, dtype=torch.int64)
+    for b in range(batch):
+        L = int(lengths[b]) if lengths is not None else int(torch.randint(2, T + 1, (1,), generator=g).item())
+        assert 2 <= L <= T, L
+        ids[b, 0] = eot - 1
+        if L > 2:
+            ids[b, 1:L - 1] = torch.randint(1, eot - 1, (L - 2,), generator=g)
+        ids[b, L - 1] = eot
+    return ids
+
+
+def clip_images(sizes, seed: int = 4242):
+    """8-bit RGB test images [H, W, 3] (a list, one per (H, W) of ``sizes``): smooth gradients plus noise, so that resampling and rounding both matter."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for (H, W) in sizes:
+        yy = torch.linspace(0, 1, H)[:, None, None]
+        xx = torch.linspace(0, 1, W)[None, :, None]
+        ph = torch.rand(3, generator=g)[None, None, :] * 6.28
+        base = 0.5 + 0.35 * torch.sin(6.0 * yy + ph) * torch.cos(5.0 * xx - ph)
+        img = (base + 0.15 * torch.randn(H, W, 3, generator=g)).clamp(0, 1)
+        out.append((img * 255.0).round().to(torch.uint8))
+    return out
 
 
 def lineart_state_dict(seed: int = 11) -> Dict[str, torch.Tensor]:

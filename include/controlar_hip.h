@@ -355,6 +355,60 @@ int car_t5_configure(car_ctx* ctx, const car_t5_config* cfg);
 int car_t5_encode(car_ctx* ctx, const int64_t* input_ids, const int64_t* attention_mask, int32_t B, int32_t T, void* out, void* stream);
 
 /*
+ * CLIP score — replaces compute_clip_score (evaluations/t2i/evaluation.py:129-176: OpenAI clip.load, preprocess, encode_image, encode_text,
+ * F.cosine_similarity, mean) on tensors that are already on the device.  The model is CLIP as HF transformers' CLIPModel evaluates it: a ViT with a
+ * bias-free patch convolution, class token, learned positions, pre_layrnorm, pre-norm layers (LayerNorm, q/k/v/out projections with bias, scale
+ * head_dim^-0.5, quick-GELU MLP), post_layernorm on the class row and visual_projection; a text transformer over token + position embeddings with the
+ * same layer under a causal mask (no padding mask), final_layer_norm, the row at the first position of the largest token id and text_projection.
+ * Configure once, load the tensors through car_load_tensor under "clip." + the HF state-dict key (text_model.embeddings.token_embedding.weight,
+ * text_model.encoder.layers.N.self_attn.q_proj.weight, vision_model.pre_layrnorm.weight, visual_projection.weight, ...; logit_scale and *.position_ids
+ * are accepted and ignored; any other "clip.*" name is refused), then car_finalize_weights, which names the first missing tensor.  A context may hold
+ * CLIP alone or next to any other model; the tensors travel in the packed cache (the importing context is configured with the same car_clip_config
+ * first).  car_clip_configure refuses a head width other than 64 in either tower (the fused attention kernel's; ViT-g/14's 88 is out of scope), an
+ * image side that is no multiple of the patch, widths and MLP widths that are no multiples of 32 (the GEMMs' K step), and a context length above 128;
+ * the context is left usable.
+ */
+typedef struct car_clip_config {
+    int32_t vision_width;     /* 768 (ViT-B/32) */
+    int32_t vision_layers;    /* 12 */
+    int32_t vision_heads;     /* 12 */
+    int32_t vision_mlp;       /* 3072 */
+    int32_t image_size;       /* n_px, 224 */
+    int32_t patch;            /* 32 */
+    int32_t text_width;       /* 512 */
+    int32_t text_layers;      /* 12 */
+    int32_t text_heads;       /* 8 */
+    int32_t text_mlp;         /* 2048 */
+    int32_t vocab_size;       /* 49408 */
+    int32_t context_length;   /* 77 */
+    int32_t proj_dim;         /* 512 */
+    float   ln_eps;           /* 1e-5 */
+    int32_t reserved[10];     /* zero */
+} car_clip_config;
+int car_clip_configure(car_ctx* ctx, const car_clip_config* cfg);
+/*
+ * img_hwc_u8: uint8 [B,H,W,3] (device), e.g. the car_pixels_to_u8 output or the evaluation-resolution image.  In this order: with requant != 0 every
+ * byte u goes through the script's ToTensor / Normalize(0.5, 0.5) / tensor2pil round trip, trunc(((u/255 - 0.5)/0.5 + 1) * 127.5) in fp32 (not the
+ * identity: 63 of the 256 values change; the input is not modified, the library works on a copy); the short side is resized to image_size with Pillow's
+ * BICUBIC (car_resize's arithmetic), the long side to int(image_size * long / short); the image_size x image_size centre is cropped with torchvision's
+ * CenterCrop offset rule (round half to even); u/255, then (x - mean)/std with CLIP's constants, each step rounded to fp32 once; the tower.
+ * out_emb: fp32 [B,proj_dim] (in CAR_BF16 mode the values are bf16-representable) or NULL; pixel_values_out: fp32 [B,3,image_size,image_size], what the
+ * tower received before the rounding to the element type, or NULL; not both NULL.
+ */
+int car_clip_encode_image(car_ctx* ctx, const uint8_t* img_hwc_u8, int32_t B, int32_t H, int32_t W, int32_t requant,
+                          float* out_emb, float* pixel_values_out, void* stream);
+/* ids: int64 [B,T] (device), T <= context_length.  out_emb: fp32 [B,proj_dim].  An id outside [0, vocab) cannot fail this call (no host read-back): it
+ * is read as token 0 and raises the sticky error flag, as car_score treats a bad token. */
+int car_clip_encode_text(car_ctx* ctx, const int64_t* ids, int32_t B, int32_t T, float* out_emb, void* stream);
+/* out_scores: fp32 [B] = F.cosine_similarity(img_emb, txt_emb, dim=1, eps=1e-8) of fp32 [B,proj_dim] inputs: each vector divided by max(its norm, eps), then
+ * the dot product; fp32, one wave per pair, a fixed shuffle tree.  out_mean: fp64 [1] = the mean of the first n_mean scores (1 <= n_mean <= B), folded
+ * by one block in a fixed order, or NULL.  Works on any context with a CLIP configuration.
+ * All three entries are deterministic (no atomics), batch-invariant per row (fixed chunks of at most 16384 activation rows; no kernel lets a row depend on its chunk-mates), do
+ * not synchronise with the host and leave the context usable after a refusal. */
+int car_clip_score(car_ctx* ctx, const float* img_emb, const float* txt_emb, int32_t B, int32_t n_mean,
+                   float* out_scores, double* out_mean, void* stream);
+
+/*
  * generate() for the class-conditional model — replaces generate.py:134-204 (c2i branch :139-154) over
  * autoregressive/models/gpt.py.  labels [B] int64 (device).  Prefix length is 1; no pad mask; control_strength
  * does not exist on this path.  NOTE: in the reference snapshot this branch only runs with cfg_scale <= 1
@@ -417,6 +471,9 @@ int car_debug_pack_decode_weight(const float* w, int32_t N, int32_t K, uint16_t*
  * (first source index, number of taps).  max_kk: the capacity of kk in elements; non-zero when it is too small or an argument is refused. */
 int car_debug_resample_coeffs(int32_t in_size, double in0, double in1, int32_t out_size, int32_t filter,
                               int32_t* ksize_out, int32_t* kk /* [out_size*ksize] */, int32_t* bounds /* [out_size*2] */, int64_t max_kk);
+
+/* Host-only: the 256-entry table of car_clip_encode_image's requant step: out[u] = trunc(clamp(((u/255 - 0.5)/0.5 + 1) * 127.5, 0, 255)) in fp32. */
+int car_debug_clip_requant_table(unsigned char* out /* [256] */);
 
 /* Host-only: fp32 -> OCP e4m3fn bytes with the library's rounding (round-to-nearest-even, saturating at 448). */
 int car_debug_f32_to_e4m3(const float* in, unsigned char* out, int64_t n);
