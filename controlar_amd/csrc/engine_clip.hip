@@ -94,13 +94,11 @@ static int clip_ready(car_ctx* c, const char* who) {
 // causal: the text tower's mask (key j <= query i, no padding mask).  Scratch: ws[2] xn, ws[3] q|k|v, ws[4] S, ws[5] P, ws[6] V^T, ws[7] mid, ws[8] ctx.
 static int clip_layers(car_ctx* c, const std::string& tower, int layers, void* h, int nb, int Tn, int D, int nh, int F, bool causal, hipStream_t st) {
     const int mode = c->mode; const size_t e = c->esz; const float eps = c->clip.ln_eps;
-    const int Tpad = (int)rup(Tn, 32); const long rows = (long)nb * Tn;
-    const bool flash = use_flash(c, 64);
-    void *xn = c->ws[2].p, *qkv = c->ws[3].p, *P = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
-    float* S = (float*)c->ws[4].p;
+    const long rows = (long)nb * Tn;
+    void *xn = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
     void* qp = qkv; void* kp = off(qkv, (size_t)rows * D, e); void* vp = off(qkv, (size_t)2 * rows * D, e);
-    const unsigned char* ones = (const unsigned char*)c->clip_ones.p;
-    const float scale = 0.125f;                                     // head_dim^-0.5, head_dim = 64
+    // ctx = softmax(Q K^T * head_dim^-0.5) V, head_dim = 64 (eager_attention_forward); the text tower's causal form takes an all-ones pad mask
+    const AttnCall at = {qp, kp, vp, D, ctx, nb, Tn, nh, 64, 0.125f, causal ? ATTN_CAUSAL : ATTN_NONE, causal ? (const unsigned char*)c->clip_ones.p : nullptr, nullptr, 0};
     auto lin = [&](const void* x, int K, const std::string& w, void* y, int N, int act, const void* R) {
         GemmP q = gp(x, K, Wp(c, w + ".weight"), K, y, N, (int)rows, N, K);
         q.bias = Wp(c, w + ".bias"); q.bias_mode = BIAS_N; q.act = act; q.R = R; q.ldr = N;
@@ -111,27 +109,7 @@ static int clip_layers(car_ctx* c, const std::string& tower, int layers, void* h
         car_launch_layernorm(mode, h, Wp(c, L + "layer_norm1.weight"), Wp(c, L + "layer_norm1.bias"), xn, rows, D, eps, st);
         if (lin(xn, D, L + "self_attn.q_proj", qp, D, ACT_NONE, nullptr) || lin(xn, D, L + "self_attn.k_proj", kp, D, ACT_NONE, nullptr) ||
             lin(xn, D, L + "self_attn.v_proj", vp, D, ACT_NONE, nullptr)) FAIL(c, "CLIP: a projection GEMM was refused (width %d)", D);
-        car_launch_transpose_pad(mode, vp, D, (long)Tn * D, vT, nb, Tn, Tpad, D, st);
-        bool fused = false;
-        if (flash) {
-            FlashP f; memset(&f, 0, sizeof(f));
-            f.q = (const bf16_t*)qp; f.k = (const bf16_t*)kp; f.vt = (const bf16_t*)vT; f.o = (bf16_t*)ctx;
-            f.q_sb = f.k_sb = f.o_sb = (long)Tn * D; f.q_st = f.k_st = f.o_st = D; f.vt_sb = (long)D * Tpad; f.vt_ld = Tpad;
-            f.Tq = f.Tk = Tn; f.H = nh; f.scale = scale; f.mode = causal ? 1 : 0; f.mask = causal ? ones : nullptr;
-            fused = car_launch_flash64(&f, nb, st) == 0;
-        }
-        if (!fused) {   // S[b,h] = (Q K^T) * head_dim^-0.5, softmax in fp32, ctx = P V (eager_attention_forward)
-            GemmP q = gp(qp, D, kp, D, S, Tn, Tn, Tn, 64);
-            q.alpha = scale; q.out_f32 = 1; q.nb0 = nb; q.nb1 = nh;
-            q.sA0 = (long)Tn * D; q.sA1 = 64; q.sW0 = (long)Tn * D; q.sW1 = 64; q.sC0 = (long)nh * Tn * Tn; q.sC1 = (long)Tn * Tn;
-            car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-            if (causal) car_launch_softmax_at(mode, S, Tn, P, Tpad, (long)nb * nh * Tn, Tn, 1, ones, Tn, nh, 0, st);
-            else car_launch_softmax(mode, S, Tn, P, Tpad, (long)nb * nh * Tn, Tn, 0, nullptr, 0, 0, st);
-            GemmP r = gp(P, Tpad, vT, Tpad, ctx, D, Tn, 64, Tpad);
-            r.nb0 = nb; r.nb1 = nh;
-            r.sA0 = (long)nh * Tn * Tpad; r.sA1 = (long)Tn * Tpad; r.sW0 = (long)D * Tpad; r.sW1 = (long)64 * Tpad; r.sC0 = (long)Tn * D; r.sC1 = 64;
-            car_launch_gemm(mode, AMODE_PLAIN, &r, st);
-        }
+        if (attn_run(c, at, st)) FAIL(c, "CLIP: the fused attention kernel refused %d rows x %d heads", Tn, nh);
         if (lin(ctx, D, L + "self_attn.out_proj", h, D, ACT_NONE, h)) FAIL(c, "CLIP: the out_proj GEMM was refused (width %d)", D);
         car_launch_layernorm(mode, h, Wp(c, L + "layer_norm2.weight"), Wp(c, L + "layer_norm2.bias"), xn, rows, D, eps, st);
         if (lin(xn, D, L + "mlp.fc1", mid, F, ACT_QUICK_GELU, nullptr) || lin(mid, F, L + "mlp.fc2", h, D, ACT_NONE, h)) FAIL(c, "CLIP: an MLP GEMM was refused (widths %d, %d)", D, F);
@@ -141,16 +119,14 @@ static int clip_layers(car_ctx* c, const std::string& tower, int layers, void* h
 
 // scratch of one chunk of `CH` sequences of Tn rows (the buffers clip_layers names, plus ws[0] patches / pooled rows and ws[1] h)
 static int clip_scratch(car_ctx* c, int CH, int Tn, int D, int nh, int F, size_t ws0_elems) {
-    const size_t e = c->esz; const long rows = (long)CH * Tn; const int Tpad = (int)rup(Tn, 32);
+    const size_t e = c->esz; const long rows = (long)CH * Tn; const AttnBytes ab = attn_bytes(c, CH, Tn, nh, 64);
     NEED(c, c->ws[0], ws0_elems * e);
     NEED(c, c->ws[1], (size_t)rows * D * e);
     NEED(c, c->ws[2], (size_t)rows * D * e);
     NEED(c, c->ws[3], (size_t)rows * 3 * D * e);
-    if (!use_flash(c, 64)) {
-        NEED(c, c->ws[4], (size_t)CH * nh * Tn * Tn * 4);
-        NEED(c, c->ws[5], (size_t)CH * nh * Tn * Tpad * e);
-    }
-    NEED(c, c->ws[6], (size_t)CH * D * Tpad * e);
+    if (ab.S) NEED(c, c->ws[4], ab.S);
+    if (ab.P) NEED(c, c->ws[5], ab.P);
+    NEED(c, c->ws[6], ab.Vt);
     NEED(c, c->ws[7], (size_t)rows * F * e);
     NEED(c, c->ws[8], (size_t)rows * D * e);
     return 0;

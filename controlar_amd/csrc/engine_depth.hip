@@ -212,11 +212,10 @@ extern "C" int car_depth(car_ctx* c, const float* pixel_values, int32_t B, int32
     NEED(c, c->ws[1], (size_t)CH * Tn * D * e);            // h
     NEED(c, c->ws[2], (size_t)CH * Tn * D * e);            // y (normed) / tok
     NEED(c, c->ws[3], (size_t)CH * Tn * 3 * D * e);        // q | k | v (separate planes)
-    if (!flash) {
-        NEED(c, c->ws[4], (size_t)CH * nh * Tn * Tn * 4);      // S fp32
-        NEED(c, c->ws[5], (size_t)CH * nh * Tn * Tpad * e);    // P
-    }
-    NEED(c, c->ws[6], (size_t)CH * D * Tpad * e);          // V^T
+    const AttnBytes ab = attn_bytes(c, CH, Tn, nh, hd);
+    if (ab.S) NEED(c, c->ws[4], ab.S);                     // S fp32
+    if (ab.P) NEED(c, c->ws[5], ab.P);                     // P
+    NEED(c, c->ws[6], ab.Vt);                              // V^T
     NEED(c, c->ws[7], (size_t)CH * Tn * d.mlp * e);        // mlp mid
     NEED(c, c->ws[8], (size_t)CH * Tn * D * e);            // ctx
     // development build only: time the backbone alone (outputs are not written), and the reference's order up-sample -> 1x1 projection (DPT section)
@@ -238,8 +237,7 @@ extern "C" int car_depth(car_ctx* c, const float* pixel_values, int32_t B, int32
     };
     for (int b0 = 0; b0 < B; b0 += CH) {
         const int nb = std::min(CH, B - b0);
-        void *patches = c->ws[0].p, *h = c->ws[1].p, *y = c->ws[2].p, *qkv = c->ws[3].p, *Pm = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
-        float* Sc = (float*)c->ws[4].p;
+        void *patches = c->ws[0].p, *h = c->ws[1].p, *y = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
         DPTCHK(c, car_launch_dpt_patchify(mode, pixel_values + (size_t)b0 * 3 * P, patches, nb, S, st));
         {   // patch projection -> y used as the token buffer, then cls | tokens + resized position embeddings (DPTViTEmbeddings.forward)
             GemmP q = gp(patches, Kp, W_(a + "embeddings.patch_embeddings.projection.weight"), Kp, y, D, nb * n, D, Kp);
@@ -259,23 +257,9 @@ extern "C" int car_depth(car_ctx* c, const float* pixel_values, int32_t B, int32
                 q.bias = W_(L + "attention.attention." + std::string(names[t]) + ".bias"); q.bias_mode = BIAS_N;
                 car_launch_gemm(mode, AMODE_PLAIN, &q, st);
             }
-            car_launch_transpose_pad(mode, vp, D, (long)Tn * D, vT, nb, Tn, Tpad, D, st);
-            if (flash) {
-                FlashP f; memset(&f, 0, sizeof(f));
-                f.q = (const bf16_t*)qp; f.k = (const bf16_t*)kp; f.vt = (const bf16_t*)vT; f.o = (bf16_t*)ctx;
-                f.q_sb = f.k_sb = f.o_sb = (long)Tn * D; f.q_st = f.k_st = f.o_st = D; f.vt_sb = (long)D * Tpad; f.vt_ld = Tpad;
-                f.Tq = f.Tk = Tn; f.H = nh; f.scale = 1.0f / std::sqrt((float)hd); f.mode = 0;
-                if (car_launch_flash64(&f, nb, st) != 0) FAIL(c, "car_depth: the fused attention kernel refused %d tokens x %d heads", Tn, nh);
-            } else {   // S[b,h] = (Q K^T) * hd^-0.5, softmax in fp32, ctx = P V   (eager_attention_forward)
-                GemmP q = gp(qp, D, kp, D, Sc, Tn, Tn, Tn, hd);
-                q.alpha = 1.0f / std::sqrt((float)hd); q.out_f32 = 1; q.nb0 = nb; q.nb1 = nh;
-                q.sA0 = (long)Tn * D; q.sA1 = hd; q.sW0 = (long)Tn * D; q.sW1 = hd; q.sC0 = (long)nh * Tn * Tn; q.sC1 = (long)Tn * Tn;
-                car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-                car_launch_softmax(mode, Sc, Tn, Pm, Tpad, (long)nb * nh * Tn, Tn, 0, nullptr, 0, 0, st);
-                GemmP r = gp(Pm, Tpad, vT, Tpad, ctx, D, Tn, hd, Tpad);
-                r.nb0 = nb; r.nb1 = nh;
-                r.sA0 = (long)nh * Tn * Tpad; r.sA1 = (long)Tn * Tpad; r.sW0 = (long)D * Tpad; r.sW1 = (long)hd * Tpad; r.sC0 = (long)Tn * D; r.sC1 = hd;
-                car_launch_gemm(mode, AMODE_PLAIN, &r, st);
+            {   // ctx = softmax(Q K^T * hd^-0.5) V   (eager_attention_forward; softmax in fp32)
+                const AttnCall at = {qp, kp, vp, D, ctx, nb, Tn, nh, hd, 1.0f / std::sqrt((float)hd), ATTN_NONE, nullptr, nullptr, 0};
+                if (attn_run(c, at, st)) FAIL(c, "car_depth: the fused attention kernel refused %d tokens x %d heads", Tn, nh);
             }
             {   // h = dense(ctx) + h
                 GemmP q = gp(ctx, D, W_(L + "attention.output.dense.weight"), D, h, D, (int)rows, D, D);

@@ -112,11 +112,10 @@ extern "C" int car_encode_control(car_ctx* c, const void* img, int32_t img_dtype
     NEED(c, c->ws[1], (size_t)CH * Tn * D * e);            // h
     NEED(c, c->ws[2], (size_t)CH * Tn * D * e);            // y (normed) / tok
     NEED(c, c->ws[3], (size_t)CH * Tn * 3 * D * e);        // q | k | v (separate planes)
-    if (!flash) {
-        NEED(c, c->ws[4], (size_t)CH * nh * Tn * Tn * 4);      // S fp32
-        NEED(c, c->ws[5], (size_t)CH * nh * Tn * Tpad * e);    // P
-    }
-    NEED(c, c->ws[6], (size_t)CH * D * Tpad * e);          // V^T
+    const AttnBytes ab = attn_bytes(c, CH, Tn, nh, hd);
+    if (ab.S) NEED(c, c->ws[4], ab.S);                     // S fp32
+    if (ab.P) NEED(c, c->ws[5], ab.P);                     // P
+    NEED(c, c->ws[6], ab.Vt);                              // V^T
     NEED(c, c->ws[7], (size_t)CH * Tn * (g.vit_mlp > g.dim ? g.vit_mlp : g.dim) * e);   // mlp mid / adapter mid
     NEED(c, c->ws[8], (size_t)CH * Tn * D * e);            // ctx
     fence_in(c, caller);
@@ -125,8 +124,7 @@ extern "C" int car_encode_control(car_ctx* c, const void* img, int32_t img_dtype
         const int nb = (B - b0) < CH ? (B - b0) : CH;
         const size_t ibytes = img_dtype == CAR_DT_BF16 ? 2 : 4;
         const void* im = (const char*)img + (size_t)b0 * 3 * H * W * ibytes;
-        void *patches = c->ws[0].p, *h = c->ws[1].p, *y = c->ws[2].p, *qkv = c->ws[3].p, *P = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
-        float* S = (float*)c->ws[4].p;
+        void *patches = c->ws[0].p, *h = c->ws[1].p, *y = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
         car_launch_patchify(mode, im, img_dtype, patches, nb, H, W, gh, gw, p, Kp, g.resize_mode == CAR_RESIZE_BICUBIC_AC, rt.iy, rt.ix, rt.wy, rt.wx, st);
         {   // patch projection (HF :119-149) -> y used as tok buffer
             GemmP q = gp(patches, Kp, Wp(c, a + "embeddings.patch_embeddings.projection.weight"), Kp, y, D, nb * n, D, Kp);
@@ -145,27 +143,9 @@ extern "C" int car_encode_control(car_ctx* c, const void* img, int32_t img_dtype
                 q.bias = Wp(c, L + "attention.attention." + std::string(names[t]) + ".bias"); q.bias_mode = BIAS_N;
                 car_launch_gemm(mode, AMODE_PLAIN, &q, st);
             }
-            car_launch_transpose_pad(mode, vp, D, (long)Tn * D, vT, nb, Tn, Tpad, D, st);
-            bool fused = false;
-            if (flash) {
-                FlashP f; memset(&f, 0, sizeof(f));
-                f.q = (const bf16_t*)qp; f.k = (const bf16_t*)kp; f.vt = (const bf16_t*)vT; f.o = (bf16_t*)ctx;
-                f.q_sb = f.k_sb = f.o_sb = (long)Tn * D; f.q_st = f.k_st = f.o_st = D; f.vt_sb = (long)D * Tpad; f.vt_ld = Tpad;
-                f.Tq = f.Tk = Tn; f.H = nh; f.scale = 1.0f / std::sqrt((float)hd); f.mode = 0;
-                fused = car_launch_flash64(&f, nb, st) == 0;
-            }
-            if (!fused) {   // S[b,h] = (Q K^T) * hd^-0.5   (HF eager_attention_forward :153-179; softmax internals fp32)
-                GemmP q = gp(qp, D, kp, D, S, Tn, Tn, Tn, hd);
-                q.alpha = 1.0f / std::sqrt((float)hd); q.out_f32 = 1; q.nb0 = nb; q.nb1 = nh;
-                q.sA0 = (long)Tn * D; q.sA1 = hd; q.sW0 = (long)Tn * D; q.sW1 = hd; q.sC0 = (long)nh * Tn * Tn; q.sC1 = (long)Tn * Tn;
-                car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-                car_launch_softmax(mode, S, Tn, P, Tpad, (long)nb * nh * Tn, Tn, 0, nullptr, 0, 0, st);
-            }
-            if (!fused) {   // ctx[b, t, h*hd + d] = P[b,h] @ V[b,h]
-                GemmP q = gp(P, Tpad, vT, Tpad, ctx, D, Tn, hd, Tpad);
-                q.nb0 = nb; q.nb1 = nh;
-                q.sA0 = (long)nh * Tn * Tpad; q.sA1 = (long)Tn * Tpad; q.sW0 = (long)D * Tpad; q.sW1 = (long)hd * Tpad; q.sC0 = (long)Tn * D; q.sC1 = hd;
-                car_launch_gemm(mode, AMODE_PLAIN, &q, st);
+            {   // ctx = softmax(Q K^T * hd^-0.5) V   (HF eager_attention_forward :153-179; softmax internals fp32)
+                const AttnCall at = {qp, kp, vp, D, ctx, nb, Tn, nh, hd, 1.0f / std::sqrt((float)hd), ATTN_NONE, nullptr, nullptr, 0};
+                if (attn_run(c, at, st)) FAIL(c, "car_encode_control: the fused attention kernel refused %d tokens x %d heads", Tn, nh);
             }
             {   // h = layer_scale1(dense(ctx)) + h   (HF :342-363)
                 GemmP q = gp(ctx, D, Wp(c, L + "attention.output.dense.weight"), D, h, D, (int)rows, D, D);

@@ -398,7 +398,6 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok, li = g.n_layer / 3;
     const int mode = c->mode; const size_t e = c->esz;
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
-    const int Tpad = (int)rup(T, 32);
 
     // ---- row layout.  Images are cut into NG groups; the rows of group g are contiguous: [cond rows | uncond rows] under CFG
     // (so every group is a self-contained chain for the decode loop), plain image order otherwise.  NG = 1 reproduces the
@@ -428,12 +427,10 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     NEED(c, c->ws[1], (size_t)rowsP * D * e);                                 // h (prefill)
     NEED(c, c->ws[2], (size_t)rowsP * D * e);                                 // xn
     NEED(c, c->ws[3], (size_t)rowsP * 3 * D * e);                             // qkv
-    const bool pf_flash = use_flash(c, 64);                                   // fused prefill attention: no score / probability tensors
-    if (!pf_flash) {
-        NEED(c, c->ws[4], (size_t)b * Hn * T * T * 4);                        // S
-        NEED(c, c->ws[5], (size_t)b * Hn * T * Tpad * e);                     // P
-    }
-    NEED(c, c->ws[6], (size_t)b * D * Tpad * e);                              // V^T
+    const AttnBytes ab = attn_bytes(c, b, T, Hn, 64);                         // fused prefill attention: no score / probability tensors
+    if (ab.S) NEED(c, c->ws[4], ab.S);                                        // S
+    if (ab.P) NEED(c, c->ws[5], ab.P);                                        // P
+    NEED(c, c->ws[6], ab.Vt);                                                 // V^T
     NEED(c, c->ws[7], (size_t)rowsP * (mode == CAR_BF16 ? Fh : 3 * Fh) * e);  // ffn mid (+ interleaved w13 out in exact mode)
     NEED(c, c->ws[8], (size_t)rowsP * D * e);                                 // attention out
     NEED(c, c->ws[9], (size_t)b * V * 4);                                     // logits fp32
@@ -508,13 +505,12 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
         pmask = (const unsigned char*)c->maskw.p;
     }
     const long rowsW = (long)b * Tv;                                           // rows the prefill computes (rowsP = b * T sized the buffers)
-    const int Tpw = (int)rup(Tv, 32);
     for (int i = 0; i < 8; ++i) { c->h_init[2 * i] = T + c->dbg_skip; c->h_init[2 * i + 1] = c->dbg_skip; }    // (pos, step) per chain: after prefill the first decode step runs at input_pos = T, sampling token index 1 (+ the profiling skip)
     car_launch_set_pos_step(pos, c->h_init[0], c->h_init[1], st);
 
     // ---- D. text prefix embed: cls_embedding.cap_proj (gpt_t2i.py:435), uncond rows = uncond_embedding (generate.py:157)
-    void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *P = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *att = c->ws[8].p;
-    float* S = (float*)c->ws[4].p; float* logits = (float*)c->ws[9].p;
+    void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *att = c->ws[8].p;
+    float* logits = (float*)c->ws[9].p;
     if (c2i) {
         // LabelEmbedder (gpt.py:89-96): h[b] = embedding_table[label]; CFG rows use the null class num_classes (generate.py:141).
         // The row -> table-index map is built on the device (no host round trip): an out-of-range label is clamped to the null class and
@@ -537,11 +533,9 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     if (use_control) {
         const int Mc = B * n_tok;
         void* ce = c->ws[11].p;
-        // scratch for the MLP hidden activations: reuse the (idle) KV area? no — use ws[7]/ws[3] sized for prefill; allocate via ws[4] if needed
+        // scratch for the MLP hidden activations: ws[4], idle until the prefill's attention (which may need it larger)
         DevBuf& scratch = c->ws[4];
-        const size_t s_bytes = pf_flash ? 0 : (size_t)b * Hn * T * T * 4;
-        NEED(c, scratch, (size_t)Mc * D * e > s_bytes ? (size_t)Mc * D * e : s_bytes);
-        S = (float*)c->ws[4].p;
+        NEED(c, scratch, std::max((size_t)Mc * D * e, ab.S));
         mlp_tanh(c, c->ctrl_in.p, D, 0, 1, Mc, D, "condition_mlp.cap_proj.", scratch.p, ce, D, st);
         for (int k = 0; k < 3; ++k) for (int gi = 0; gi < NG; ++gi) {
             const int ng = img0[gi + 1] - img0[gi]; const size_t rows = (size_t)ng * n_tok, base = (size_t)mult * img0[gi] * n_tok;
@@ -562,38 +556,11 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
         { GemmP q = gp(xn, D, Wp(c, L + "attention.wqkv.weight"), D, qkv, 3 * D, (int)rowsW, 3 * D, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
         if (fast) car_launch_prefill_rope_kv2(qkv, off(c->kv.p, (size_t)(2 * l) * kv_layer, kv_e), off(c->kv.p, (size_t)(2 * l + 1) * kv_layer, kv_e), c->rope, b, Tv, Hn, D, SA, g.kv_cache_fp8 ? 1 : 0, t0, st);
         else car_launch_prefill_rope_kv(mode, qkv, off(c->kv.p, (size_t)(2 * l) * kv_layer, e), off(c->kv.p, (size_t)(2 * l + 1) * kv_layer, e), c->rope, b, Tv, Hn, D, S_max, t0, st);
-        car_launch_transpose_pad(mode, off(qkv, (size_t)2 * D, e), 3 * D, (long)Tv * 3 * D, vT, b, Tv, Tpw, D, st);
-        bool fused = false;
-        if (pf_flash) {
-            FlashP f; memset(&f, 0, sizeof(f));
-            f.q = (const bf16_t*)qkv; f.k = (const bf16_t*)qkv + D; f.vt = (const bf16_t*)vT; f.o = (bf16_t*)att;
-            f.q_sb = f.k_sb = (long)Tv * 3 * D; f.q_st = f.k_st = 3 * D; f.vt_sb = (long)D * Tpw; f.vt_ld = Tpw; f.o_sb = (long)Tv * D; f.o_st = D;
-            f.Tq = f.Tk = Tv; f.H = Hn; f.scale = 0.125f; f.mode = 1; f.mask = pmask;
-            fused = car_launch_flash64(&f, b, st) == 0;
+        {   // causal + pad mask over the window's columns [t0, T); q | k | v packed in the wqkv output
+            const AttnCall at = {qkv, off(qkv, (size_t)D, e), off(qkv, (size_t)2 * D, e), 3 * D, att, b, Tv, Hn, 64, 0.125f, ATTN_CAUSAL, pmask, nullptr, t0};
+            if (attn_run(c, at, st)) FAIL(c, "car_generate: the fused attention kernel rejected the prefill's shape (dim=%d, rows per sequence=%d)", D, Tv);
         }
-        if (!fused) {
-            GemmP q = gp(qkv, 3 * D, off(qkv, (size_t)D, e), 3 * D, S, Tv, Tv, Tv, 64);
-            q.alpha = 0.125f; q.out_f32 = 1; q.nb0 = b; q.nb1 = Hn;
-            q.sA0 = (long)Tv * 3 * D; q.sA1 = 64; q.sW0 = (long)Tv * 3 * D; q.sW1 = 64; q.sC0 = (long)Hn * Tv * Tv; q.sC1 = (long)Tv * Tv;
-            car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-            car_launch_softmax_at(mode, S, Tv, P, Tpw, (long)b * Hn * Tv, Tv, 1, pmask, Tv, Hn, t0, st);
-        }
-        if (!fused) {
-            GemmP q = gp(P, Tpw, vT, Tpw, att, D, Tv, 64, Tpw);
-            q.nb0 = b; q.nb1 = Hn;
-            q.sA0 = (long)Hn * Tv * Tpw; q.sA1 = (long)Tv * Tpw; q.sW0 = (long)D * Tpw; q.sW1 = (long)64 * Tpw; q.sC0 = (long)Tv * D; q.sC1 = 64;
-            car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-        }
-        { GemmP q = gp(att, D, Wp(c, L + "attention.wo.weight"), D, h, D, (int)rowsW, D, D); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
-        { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, L + "ffn_norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rowsW, st); }
-        if (mode == CAR_BF16) {
-            GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid, Fh, (int)rowsW, 2 * Fh, D); q.swiglu = 1; car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-        } else {
-            void* mid2 = off(mid, (size_t)rowsW * Fh, e);
-            GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid2, 2 * Fh, (int)rowsW, 2 * Fh, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-            car_launch_swiglu(mode, mid2, mid, rowsW, Fh, st);
-        }
-        { GemmP q = gp(mid, Fh, Wp(c, L + "feed_forward.w2.weight"), Fh, h, D, (int)rowsW, D, Fh); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
+        gpt_layer_tail(c, L, h, xn, att, mid, rowsW, st);
     }
     // final norm + logits for the LAST prefix row only (generate.py:60 samples logits[:, -1])
     { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, "norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rowsW, st); }

@@ -1,7 +1,9 @@
 // engine_internal.h — what the translation units of the host side share (engine.hip: lifecycle / stats / standalone sampler; engine_weights.hip: weight
-// packing, finalize, the packed-image cache; engine_encode.hip: resize tables, the control encoder, Canny; engine_generate.hip: prefill, the decode step,
-// generate; engine_t5.hip: the caption encoder; engine_vq.hip: VQ encode / decode; engine_score.hip: car_score).  Round 4 cut the single 1900-line engine.hip along its stage banners:
-// no behaviour change.  Everything here is internal: the C ABI is include/controlar_hip.h.
+// packing, finalize, the packed-image cache; engine_attn.hip: the batched multi-head attention every transformer stage calls (attn_bytes / attn_run) and the
+// GPT layer tail shared by the prefill and car_score; engine_encode.hip: resize tables, the control encoder, Canny; engine_generate.hip: prefill, the decode
+// step, generate; engine_score.hip: car_score; engine_t5.hip: the caption encoder; engine_clip.hip: the CLIP score; engine_vq.hip: VQ encode / decode;
+// engine_depth.hip, engine_hed.hip, engine_lineart.hip: the control extractors; engine_resize.hip, engine_metrics.hip).  Round 4 cut the single 1900-line
+// engine.hip along its stage banners: no behaviour change.  Everything here is internal: the C ABI is include/controlar_hip.h.
 #pragma once
 #include "car_common.h"
 #include "../../include/controlar_hip.h"
@@ -261,6 +263,20 @@ static inline bool use_flash(const car_ctx* c, int head_dim) {
     static const bool off_env = CAR_KNOB("CAR_NO_FLASH") != nullptr;
     return c->mode == CAR_BF16 && head_dim == 64 && !off_env;
 }
+
+// engine_attn.hip — multi-head attention over [nb, T, H*hd] rows.  q, k, v: row stride `ld` elements (the width for separate planes, 3 * width for the packed
+// wqkv output), sequence stride T * ld, head h at column h * hd; out: dense [nb, T, H*hd].  Scratch: ws[4] S (fp32 scores), ws[5] P, ws[6] V^T (keys zero padded
+// to a multiple of 32), which the caller sizes with attn_bytes for its largest chunk; S and P are 0 bytes when the fused kernel runs (use_flash).
+enum { ATTN_NONE = 0, ATTN_CAUSAL = 1, ATTN_T5 = 2 };      // = FlashP::mode: no mask | causal + pad mask [nb][T], window starting at column col0 | bias [H][T][T] + key mask [nb][T]
+struct AttnCall {
+    const void *q, *k, *v; long ld; void* out;
+    int nb, T, H, hd; float scale;
+    int kind; const unsigned char* mask; const float* bias; int col0;
+};
+struct AttnBytes { size_t S, P, Vt; };
+AttnBytes attn_bytes(const car_ctx* c, int nb, int T, int H, int hd);
+int attn_run(car_ctx* c, const AttnCall& a, hipStream_t st);      // non-zero: the fused kernel refused the shape, nothing further was launched — fail the call
+void gpt_layer_tail(car_ctx* c, const std::string& L, void* h, void* xn, const void* att, void* mid, long rows, hipStream_t st);
 
 // y = fc2(gelu_tanh(fc1 x))   (gpt_t2i.py:165-181), x: [z][M, K] with row stride lda / batch stride sA
 static inline void mlp_tanh(car_ctx* c, const void* x, long lda, long sA, int nb, int M, int K, const std::string& pfx, void* mid, void* y, int dim, hipStream_t st) {

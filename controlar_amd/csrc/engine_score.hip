@@ -82,7 +82,7 @@ extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, c
         if (Tv % 8) { Tv = T; t0 = 0; }
         if (hinted && t0 > 0) car_launch_min_int(jmin, B, jmin_min, t0, c->host_flags + 1, st);
     }
-    const int Ts = Tv + n_new - 1, Tps = (int)rup((size_t)Ts, 32);
+    const int Ts = Tv + n_new - 1;
     int nc = kScoreRows / (mult * Ts); if (nc < 1) nc = 1; if (nc > B) nc = B;
     const bool pf_flash = use_flash(c, 64);
     if (!pf_flash) while (nc > 1 && (size_t)nc * mult * Hn * Ts * Ts * 4 > kScoreTensorCap) --nc;
@@ -95,16 +95,16 @@ extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     NEED(c, c->ws[1], (size_t)rowsC * D * e);
     NEED(c, c->ws[2], (size_t)rowsC * D * e);
     NEED(c, c->ws[3], (size_t)rowsC * 3 * D * e);
-    { size_t s4 = use_control ? (size_t)B * n_tok * D * e : 0; if (!pf_flash) s4 = std::max(s4, (size_t)bc * Hn * Ts * Ts * 4); if (s4) NEED(c, c->ws[4], s4); }
-    if (!pf_flash) NEED(c, c->ws[5], (size_t)bc * Hn * Ts * Tps * e);
-    NEED(c, c->ws[6], (size_t)bc * D * Tps * e);
+    const AttnBytes ab = attn_bytes(c, bc, Ts, Hn, 64);
+    { const size_t s4 = std::max(use_control ? (size_t)B * n_tok * D * e : 0, ab.S); if (s4) NEED(c, c->ws[4], s4); }      // control-MLP scratch, then S
+    if (ab.P) NEED(c, c->ws[5], ab.P);
+    NEED(c, c->ws[6], ab.Vt);
     NEED(c, c->ws[7], (size_t)rowsC * (fast ? Fh : 3 * Fh) * e);
     NEED(c, c->ws[8], (size_t)rowsC * D * e);
     NEED(c, c->ws[10], (size_t)nparts * nc * n_new * 16);
     NEED(c, c->maskw, (size_t)bc * Ts);
     if (use_control) { NEED(c, c->ws[11], (size_t)B * n_tok * D * e); for (int k = 0; k < 3; ++k) NEED(c, c->ctrl[k], (size_t)b * n_tok * D * e); }
-    void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *P = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *att = c->ws[8].p;
-    float* S = (float*)c->ws[4].p;
+    void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *att = c->ws[8].p;
 
     // ---- C. control tokens of every chunk: condition_mlp, then the 3 condition_layers (gpt_t2i.py:437-442); rows [cond | zeros] per chunk
     if (use_control) {
@@ -141,36 +141,9 @@ extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, c
             }
             { GemmP q = gp(xn, D, Wp(c, L + "attention.wqkv.weight"), D, qkv, 3 * D, (int)rows, 3 * D, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
             car_launch_score_rope(mode, qkv, c->rope, nseq, Ts, Hn, D, t0, st);
-            car_launch_transpose_pad(mode, off(qkv, (size_t)2 * D, e), 3 * D, (long)Ts * 3 * D, vT, nseq, Ts, Tps, D, st);
-            bool fused = false;
-            if (pf_flash) {
-                FlashP f; memset(&f, 0, sizeof(f));
-                f.q = (const bf16_t*)qkv; f.k = (const bf16_t*)qkv + D; f.vt = (const bf16_t*)vT; f.o = (bf16_t*)att;
-                f.q_sb = f.k_sb = (long)Ts * 3 * D; f.q_st = f.k_st = 3 * D; f.vt_sb = (long)D * Tps; f.vt_ld = Tps; f.o_sb = (long)Ts * D; f.o_st = D;
-                f.Tq = f.Tk = Ts; f.H = Hn; f.scale = 0.125f; f.mode = 1; f.mask = maskx;
-                fused = car_launch_flash64(&f, nseq, st) == 0;
-                if (!fused) { rc = -2; break; }      // (the unfused buffers were not sized: flash64 takes every shape this pass builds)
-            } else {
-                GemmP q = gp(qkv, 3 * D, off(qkv, (size_t)D, e), 3 * D, S, Ts, Ts, Ts, 64);
-                q.alpha = 0.125f; q.out_f32 = 1; q.nb0 = nseq; q.nb1 = Hn;
-                q.sA0 = (long)Ts * 3 * D; q.sA1 = 64; q.sW0 = (long)Ts * 3 * D; q.sW1 = 64; q.sC0 = (long)Hn * Ts * Ts; q.sC1 = (long)Ts * Ts;
-                car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-                car_launch_softmax_at(mode, S, Ts, P, Tps, (long)nseq * Hn * Ts, Ts, 1, maskx, Ts, Hn, t0, st);
-                GemmP r = gp(P, Tps, vT, Tps, att, D, Ts, 64, Tps);
-                r.nb0 = nseq; r.nb1 = Hn;
-                r.sA0 = (long)Hn * Ts * Tps; r.sA1 = (long)Ts * Tps; r.sW0 = (long)D * Tps; r.sW1 = (long)64 * Tps; r.sC0 = (long)Ts * D; r.sC1 = 64;
-                car_launch_gemm(mode, AMODE_PLAIN, &r, st);
-            }
-            { GemmP q = gp(att, D, Wp(c, L + "attention.wo.weight"), D, h, D, (int)rows, D, D); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
-            { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, L + "ffn_norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rows, st); }
-            if (fast) {
-                GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid, Fh, (int)rows, 2 * Fh, D); q.swiglu = 1; car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-            } else {
-                void* mid2 = off(mid, (size_t)rows * Fh, e);
-                GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid2, 2 * Fh, (int)rows, 2 * Fh, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-                car_launch_swiglu(mode, mid2, mid, rows, Fh, st);
-            }
-            { GemmP q = gp(mid, Fh, Wp(c, L + "feed_forward.w2.weight"), Fh, h, D, (int)rows, D, Fh); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
+            const AttnCall at = {qkv, off(qkv, (size_t)D, e), off(qkv, (size_t)2 * D, e), 3 * D, att, nseq, Ts, Hn, 64, 0.125f, ATTN_CAUSAL, maskx, nullptr, t0};
+            if (attn_run(c, at, st)) { rc = -2; break; }      // flash64 takes every shape this pass builds (engine_attn.hip)
+            gpt_layer_tail(c, L, h, xn, att, mid, rows, st);
         }
         if (rc) break;
         { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, "norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rows, st); }

@@ -73,7 +73,7 @@ extern "C" int car_t5_encode(car_ctx* c, const int64_t* input_ids, const int64_t
     if (!input_ids || !out || B <= 0 || T <= 0) FAIL(c, "car_t5_encode: bad arguments");
     const car_t5_config& t = c->t5;
     const int mode = c->mode; const size_t e = c->esz;
-    const int D = t.d_model, nh = t.num_heads, hd = t.d_kv, inner = nh * hd, F = t.d_ff, Tpad = (int)rup(T, 32);
+    const int D = t.d_model, nh = t.num_heads, hd = t.d_kv, inner = nh * hd, F = t.d_ff;
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
     // position bias [heads][T][T] for this T (compute_bias): table[bucket(j - i)][h]
     if (c->t5_bias_T != T) {
@@ -94,14 +94,13 @@ extern "C" int car_t5_encode(car_ctx* c, const int64_t* input_ids, const int64_t
     NEED(c, c->t5_in, o_st + 2 * (size_t)n_tok * 8);
     int* ids32 = (int*)c->t5_in.p; unsigned char* mk = (unsigned char*)c->t5_in.p + o_mk; long long* stage = (long long*)((char*)c->t5_in.p + o_st);
     int CH = B; if (CH > 64) CH = 64;
-    const bool flash = use_flash(c, hd);
-    const long rows_max = (long)CH * T;
+    const long rows_max = (long)CH * T; const AttnBytes ab = attn_bytes(c, CH, T, nh, hd);
     NEED(c, c->ws[1], (size_t)n_tok * D * e);                 // h (all rows: gathered up front)
     NEED(c, c->ws[2], (size_t)rows_max * D * e);              // xn
     NEED(c, c->ws[3], (size_t)rows_max * 3 * inner * e);      // q | k | v planes
-    NEED(c, c->ws[4], (size_t)CH * nh * T * T * 4);           // S fp32
-    NEED(c, c->ws[5], (size_t)CH * nh * T * Tpad * e);        // P
-    NEED(c, c->ws[6], (size_t)CH * inner * Tpad * e);         // V^T
+    if (ab.S) NEED(c, c->ws[4], ab.S);                        // S fp32: the fp32 mode, and heads that are not 64 wide
+    if (ab.P) NEED(c, c->ws[5], ab.P);                        // P
+    NEED(c, c->ws[6], ab.Vt);                                 // V^T
     NEED(c, c->ws[7], (size_t)rows_max * F * e);              // gated mid
     NEED(c, c->ws[8], (size_t)rows_max * inner * e);          // ctx
     if (mode == CAR_F32) NEED(c, c->ws[9], (size_t)rows_max * 2 * F * e);   // exact mode: wi_0 | wi_1 outputs before the gate
@@ -117,8 +116,7 @@ extern "C" int car_t5_encode(car_ctx* c, const int64_t* input_ids, const int64_t
     for (int b0 = 0; b0 < B; b0 += CH) {
         const int nb = (B - b0) < CH ? (B - b0) : CH;
         const long rows = (long)nb * T;
-        void *h = off(c->ws[1].p, (size_t)b0 * T * D, e), *xn = c->ws[2].p, *qkv = c->ws[3].p, *P = c->ws[5].p, *vT = c->ws[6].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
-        float* S = (float*)c->ws[4].p;
+        void *h = off(c->ws[1].p, (size_t)b0 * T * D, e), *xn = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *ctx = c->ws[8].p;
         void* qp = qkv; void* kp = off(qkv, (size_t)rows * inner, e); void* vp = off(qkv, (size_t)2 * rows * inner, e);
         auto norm = [&](const std::string& w, void* dst) {
             NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = dst; np.w = Wp(c, w); np.D = D; np.eps = t.ln_eps;
@@ -132,27 +130,9 @@ extern "C" int car_t5_encode(car_ctx* c, const int64_t* input_ids, const int64_t
                 GemmP q = gp(xn, D, Wp(c, L + "0.SelfAttention." + names[k] + ".weight"), D, dst[k], inner, (int)rows, inner, D);
                 car_launch_gemm(mode, AMODE_PLAIN, &q, st);
             }
-            car_launch_transpose_pad(mode, vp, inner, (long)T * inner, vT, nb, T, Tpad, inner, st);
-            bool fused = false;
-            if (flash) {
-                FlashP f; memset(&f, 0, sizeof(f));
-                f.q = (const bf16_t*)qp; f.k = (const bf16_t*)kp; f.vt = (const bf16_t*)vT; f.o = (bf16_t*)ctx;
-                f.q_sb = f.k_sb = f.o_sb = (long)T * inner; f.q_st = f.k_st = f.o_st = inner; f.vt_sb = (long)inner * Tpad; f.vt_ld = Tpad;
-                f.Tq = f.Tk = T; f.H = nh; f.scale = 1.0f; f.mode = 2; f.mask = mk + (size_t)b0 * T; f.bias = bias;
-                fused = car_launch_flash64(&f, nb, st) == 0;
-            }
-            if (!fused) {   // scores[b,h] = Q K^T (scaling 1.0)
-                GemmP q = gp(qp, inner, kp, inner, S, T, T, T, hd);
-                q.out_f32 = 1; q.nb0 = nb; q.nb1 = nh;
-                q.sA0 = (long)T * inner; q.sA1 = hd; q.sW0 = (long)T * inner; q.sW1 = hd; q.sC0 = (long)nh * T * T; q.sC1 = (long)T * T;
-                car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-                car_launch_t5_softmax(mode, S, T, P, Tpad, (long)nb * nh * T, T, bias, mk + (size_t)b0 * T, T, nh, st);
-            }
-            if (!fused) {   // ctx[b, t, h*hd + d] = P[b,h] @ V[b,h]
-                GemmP q = gp(P, Tpad, vT, Tpad, ctx, inner, T, hd, Tpad);
-                q.nb0 = nb; q.nb1 = nh;
-                q.sA0 = (long)nh * T * Tpad; q.sA1 = (long)T * Tpad; q.sW0 = (long)inner * Tpad; q.sW1 = (long)hd * Tpad; q.sC0 = (long)T * inner; q.sC1 = hd;
-                car_launch_gemm(mode, AMODE_PLAIN, &q, st);
+            {   // ctx = softmax(Q K^T + position bias, padded keys masked) V: scaling 1.0
+                const AttnCall at = {qp, kp, vp, inner, ctx, nb, T, nh, hd, 1.0f, ATTN_T5, mk + (size_t)b0 * T, bias, 0};
+                if (attn_run(c, at, st)) FAIL(c, "car_t5_encode: the fused attention kernel refused %d tokens x %d heads", T, nh);
             }
             {   // h = h + o(ctx)   (T5LayerSelfAttention)
                 GemmP q = gp(ctx, inner, Wp(c, L + "0.SelfAttention.o.weight"), inner, h, D, (int)rows, D, inner);
