@@ -71,6 +71,15 @@ class CarSampling(C.Structure):
     ]
 
 
+class CarSamplingRow(C.Structure):
+    """car_sampling_row: the per-image sampling parameters of the car_*_rows entries (40 bytes)."""
+    _fields_ = [
+        ("cfg_scale", C.c_float), ("cfg_interval", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32),
+        ("top_p", C.c_float), ("sample_logits", C.c_int32), ("seed", C.c_uint64), ("control_strength", C.c_float),
+        ("rng_stream", C.c_uint32),
+    ]
+
+
 class CarStats(C.Structure):
     _fields_ = [
         ("decode_ms", C.c_double), ("prefill_ms", C.c_double), ("decode_steps", C.c_int64), ("decode_algo_bytes", C.c_int64),
@@ -107,6 +116,15 @@ SYMBOLS = {
     "car_debug_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_sample_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CarSampling), C.c_int32, C.c_void_p, C.c_void_p]),
+    # the same four with one car_sampling_row per image (a host array of B entries) behind `sp`
+    "car_generate_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(CarSampling), C.POINTER(CarSamplingRow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_generate_c2i_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CarSampling), C.POINTER(CarSamplingRow),
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                 C.POINTER(CarSampling), C.POINTER(CarSamplingRow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_sample_logits_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(CarSampling), C.POINTER(CarSamplingRow), C.c_int32,
+                                         C.c_void_p, C.c_void_p]),
     "car_canny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -99,7 +99,7 @@ extern "C" void car_destroy(car_ctx* c) {
     for (auto& kv : c->resize_cache) { (void)hipFree(kv.second.iy); (void)hipFree(kv.second.ix); if (kv.second.wy) (void)hipFree(kv.second.wy); if (kv.second.wx) (void)hipFree(kv.second.wx); }
     if (c->rope) (void)hipFree(c->rope);
     c->ctrl_in.release(); for (auto& b : c->ctrl) b.release(); c->kv.release(); for (auto& b : c->ws) b.release();
-    c->scal.release(); c->tok_out.release(); c->maskb.release(); c->maskw.release(); c->dec_parts.release(); c->rowimg.release(); c->rowunc.release(); if (c->host_flags) { (void)hipHostFree(c->host_flags); c->host_flags = nullptr; } c->canny_map.release(); c->lineart_ws.release(); c->hed_ws.release(); c->depth_ws.release(); c->resize_ws.release(); c->metrics_ws.release(); for (auto& a : c->rs_axis) { a.d_kk.release(); a.d_bounds.release(); } if (c->ev_rs) (void)hipEventDestroy(c->ev_rs); c->t5_in.release(); c->t5_bias.release(); c->clip_u8.release(); c->clip_ones.release();
+    c->scal.release(); c->rows_dev.release(); c->row_scale.release();c->tok_out.release(); c->maskb.release(); c->maskw.release(); c->dec_parts.release(); c->rowimg.release(); c->rowunc.release(); if (c->host_flags) { (void)hipHostFree(c->host_flags); c->host_flags = nullptr; } c->canny_map.release(); c->lineart_ws.release(); c->hed_ws.release(); c->depth_ws.release(); c->resize_ws.release(); c->metrics_ws.release(); for (auto& a : c->rs_axis) { a.d_kk.release(); a.d_bounds.release(); } if (c->ev_rs) (void)hipEventDestroy(c->ev_rs); c->t5_in.release(); c->t5_bias.release(); c->clip_u8.release(); c->clip_ones.release();
     (void)hipEventDestroy(c->ev_in); (void)hipEventDestroy(c->ev_out); (void)hipEventDestroy(c->ev_t0); (void)hipEventDestroy(c->ev_t1); (void)hipEventDestroy(c->ev_t2);
     (void)hipStreamDestroy(c->stream);
     for (int i = 0; i < 7; ++i) { (void)hipStreamDestroy(c->streamx[i]); (void)hipEventDestroy(c->ev_joinx[i]); (void)hipEventDestroy(c->ev_phase[i]); }
@@ -109,24 +109,35 @@ extern "C" void car_destroy(car_ctx* c) {
 
 // sample() of generate.py:59-74 as a standalone entry (tests; also usable by callers that bring their own logits):
 // logits fp32 [rows, V] (rows = 2B under CFG: cond then uncond), out int32 [B].  `step` only feeds the RNG counter / cfg_interval.
-extern "C" int car_sample_logits(car_ctx* c, const float* logits, int32_t B, int32_t V, const car_sampling* sp, int32_t step, int32_t* out, void* stream_) {
+// Row mode (rows != NULL, car_sample_logits_rows): image i samples with rows[i] at the Philox counter (step * 65536 + rng_stream, 0).
+static int sample_logits_impl(car_ctx* c, const float* logits, int32_t B, int32_t V, const car_sampling* sp, const car_sampling_row* rows, int32_t step, int32_t* out, void* stream_) {
     if (!c || !logits || !sp || !out || B <= 0 || V <= 0 || V % 4 || V > 32768) { if (c) c->err = "car_sample_logits: bad arguments (V must be a multiple of 4, <= 32768)"; return -1; }
     if (check_sticky(c)) return -1;
+    RowInfo ri = {sp->cfg_scale > 1.0f, sp->sample_logits != 0};
+    if (rows && rows_check(c, "car_sample_logits_rows", rows, B, V, &ri)) return -1;
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
     NEED(c, c->scal, (size_t)(16 + 2 * B) * 4);
     int* stepd = (int*)c->scal.p + 1; int* cur = (int*)c->scal.p + 16;
     fence_in(c, caller);
     SampleP p; memset(&p, 0, sizeof(p));
-    p.logits = logits; p.B = B; p.V = V; p.use_cfg = sp->cfg_scale > 1.0f; p.cfg_scale = sp->cfg_scale; p.cfg_interval = sp->cfg_interval;
+    p.logits = logits; p.B = B; p.V = V; p.use_cfg = ri.use_cfg; p.cfg_scale = sp->cfg_scale; p.cfg_interval = sp->cfg_interval;
     p.step_ptr = stepd; p.n_new = 1; p.out_tokens = out; p.cur_tok = cur;
-    p.stochastic = sp->sample_logits != 0; p.temperature = sp->temperature; p.top_k = sp->top_k; p.top_p = sp->top_p; p.seed = sp->seed;
-    // out_tokens is indexed [i*n_new + step]: n_new = 1 and a zero step pointer keep it dense; the RNG step goes through row0
+    p.stochastic = ri.any_stochastic; p.temperature = sp->temperature; p.top_k = sp->top_k; p.top_p = sp->top_p; p.seed = sp->seed;
+    if (rows) { if (rows_upload(c, rows, B, st)) return -1; p.rows = (const SampleRow*)c->rows_dev.p; }
+    // out_tokens is indexed [i*n_new + step]: n_new = 1 and a zero step pointer keep it dense; the RNG step goes through row0, the cfg_interval test's through mix_step0
     HIPCHK(c, hipMemsetAsync(stepd, 0, 4, st));           // no host source buffer, no wait: the entry only enqueues
-    p.row0 = step * 65536;
+    p.row0 = step * 65536; p.mix_step0 = step;
     car_launch_sample_greedy(&p, st);
     fence_out(c, caller);
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+extern "C" int car_sample_logits(car_ctx* c, const float* logits, int32_t B, int32_t V, const car_sampling* sp, int32_t step, int32_t* out, void* stream_) {
+    return sample_logits_impl(c, logits, B, V, sp, nullptr, step, out, stream_);
+}
+extern "C" int car_sample_logits_rows(car_ctx* c, const float* logits, int32_t B, int32_t V, const car_sampling* sp, const car_sampling_row* rows, int32_t step,
+                                      int32_t* out, void* stream_) {
+    return sample_logits_impl(c, logits, B, V, sp, rows, step, out, stream_);
 }
 
 // Waits for everything enqueued on the context's stream, then reports (and clears) sticky device-side errors — the way to learn NOW whether the

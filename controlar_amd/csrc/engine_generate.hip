@@ -350,30 +350,40 @@ extern "C" int car_debug_attn_edge_mask(int32_t lo, int32_t hi, unsigned char* k
 }
 
 // ------------------------------------------------------------------------------------- generate
+// `rows` (row mode, the *_rows entries): one car_sampling_row per image on the host, or NULL = the plain call, every image sampling with `sp`.
 static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* labels, const int64_t* emb_mask, int32_t B, int32_t n_new,
-                         int32_t use_control, const car_sampling* sp, int32_t* out_tokens, const int32_t* forced_tokens,
+                         int32_t use_control, const car_sampling* sp, const car_sampling_row* rows, int32_t* out_tokens, const int32_t* forced_tokens,
                          float* logits_out, void* stream_);
 
-extern "C" int car_generate(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask, int32_t B, int32_t n_new,
-                            int32_t use_control, const car_sampling* sp, int32_t* out_tokens, const int32_t* forced_tokens,
-                            float* logits_out, void* stream_) {
+extern "C" int car_generate_rows(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask, int32_t B, int32_t n_new,
+                                 int32_t use_control, const car_sampling* sp, const car_sampling_row* rows, int32_t* out_tokens, const int32_t* forced_tokens,
+                                 float* logits_out, void* stream_) {
     if (!c) return -1;
     if (c->cfg.model_type != 0) FAIL(c, "car_generate: context was created for the c2i model; use car_generate_c2i");
     if (!text_emb) FAIL(c, "car_generate: bad arguments");
     if (text_dtype != CAR_DT_F32 && text_dtype != CAR_DT_BF16) FAIL(c, "car_generate: text dtype must be F32 or BF16");
-    return generate_impl(c, text_emb, text_dtype, nullptr, emb_mask, B, n_new, use_control, sp, out_tokens, forced_tokens, logits_out, stream_);
+    return generate_impl(c, text_emb, text_dtype, nullptr, emb_mask, B, n_new, use_control, sp, rows, out_tokens, forced_tokens, logits_out, stream_);
+}
+extern "C" int car_generate(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask, int32_t B, int32_t n_new,
+                            int32_t use_control, const car_sampling* sp, int32_t* out_tokens, const int32_t* forced_tokens,
+                            float* logits_out, void* stream_) {
+    return car_generate_rows(c, text_emb, text_dtype, emb_mask, B, n_new, use_control, sp, nullptr, out_tokens, forced_tokens, logits_out, stream_);
 }
 
-extern "C" int car_generate_c2i(car_ctx* c, const int64_t* labels, int32_t B, int32_t n_new, int32_t use_control, const car_sampling* sp,
-                                int32_t* out_tokens, const int32_t* forced_tokens, float* logits_out, void* stream_) {
+extern "C" int car_generate_c2i_rows(car_ctx* c, const int64_t* labels, int32_t B, int32_t n_new, int32_t use_control, const car_sampling* sp,
+                                     const car_sampling_row* rows, int32_t* out_tokens, const int32_t* forced_tokens, float* logits_out, void* stream_) {
     if (!c) return -1;
     if (c->cfg.model_type != 1) FAIL(c, "car_generate_c2i: context was created for the t2i model; use car_generate");
     if (!labels) FAIL(c, "car_generate_c2i: bad arguments");
-    return generate_impl(c, nullptr, CAR_DT_F32, labels, nullptr, B, n_new, use_control, sp, out_tokens, forced_tokens, logits_out, stream_);
+    return generate_impl(c, nullptr, CAR_DT_F32, labels, nullptr, B, n_new, use_control, sp, rows, out_tokens, forced_tokens, logits_out, stream_);
+}
+extern "C" int car_generate_c2i(car_ctx* c, const int64_t* labels, int32_t B, int32_t n_new, int32_t use_control, const car_sampling* sp,
+                                int32_t* out_tokens, const int32_t* forced_tokens, float* logits_out, void* stream_) {
+    return car_generate_c2i_rows(c, labels, B, n_new, use_control, sp, nullptr, out_tokens, forced_tokens, logits_out, stream_);
 }
 
 static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* labels, const int64_t* emb_mask, int32_t B, int32_t n_new,
-                         int32_t use_control, const car_sampling* sp, int32_t* out_tokens, const int32_t* forced_tokens,
+                         int32_t use_control, const car_sampling* sp, const car_sampling_row* rows, int32_t* out_tokens, const int32_t* forced_tokens,
                          float* logits_out, void* stream_) {
     if (check_sticky(c)) return -1;
 #ifdef CAR_DEV_KNOBS
@@ -385,14 +395,20 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     if (!sp || !out_tokens || B <= 0 || n_new <= 0) FAIL(c, "car_generate: bad arguments");
     const car_config& g = c->cfg;
     const bool c2i = g.model_type == 1;
-    if (sp->sample_logits && g.vocab_size > 32768) FAIL(c, "car_generate: stochastic sampling supports vocab_size <= 32768");
+    RowInfo ri = {sp->cfg_scale > 1.0f, sp->sample_logits != 0};
+    if (rows) { if (rows_check(c, c2i ? "car_generate_c2i_rows" : "car_generate_rows", rows, B, g.vocab_size, &ri)) return -1; }
+    else if (sp->sample_logits && g.vocab_size > 32768) FAIL(c, "car_generate: stochastic sampling supports vocab_size <= 32768");
     if (g.vocab_size % 4) FAIL(c, "car_generate: vocab_size must be a multiple of 4");
     const int T = g.cls_token_num;
     if (n_new > g.block_size) FAIL(c, "car_generate: max_new_tokens %d exceeds block_size %d (rope table rows, gpt_t2i.py:454)", n_new, g.block_size);
     if (use_control && (c->ctrl_B != B || c->ctrl_ntok < n_new)) FAIL(c, "car_generate: control tokens cached for B=%d n=%d, requested B=%d n_new=%d", c->ctrl_B, c->ctrl_ntok, B, n_new);
-    const bool use_cfg = sp->cfg_scale > 1.0f;
+    const bool use_cfg = ri.use_cfg;
     const int b = use_cfg ? 2 * B : B;
-    const float cs = (use_cfg && !c2i) ? sp->control_strength : 1.0f;   // generate.py:87-92: strength ignored when cfg <= 1; absent in gpt.py
+    // generate.py:87-92: strength ignored when cfg <= 1; absent in gpt.py.  Row mode: every image's strength is folded into its control tokens once (stage C
+    // below) and the kernels run at cs = 1 — the decode-loop kernels keep their scalar strength.
+    const float cs = (use_cfg && !c2i && !rows) ? sp->control_strength : 1.0f;
+    bool row_strength = false;
+    if (rows && use_cfg && !c2i && use_control) for (int i = 0; i < B; ++i) row_strength |= rows[i].control_strength != 1.0f;
     const int S_max = (int)rup(T + n_new, 8);                       // gpt_t2i.py:395
     const int SA = c->mode == CAR_BF16 ? (int)rup(S_max, 32) : S_max;   // fast mode: packed KV streams hold whole 32-position blocks (decode2.hip)
     const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok, li = g.n_layer / 3;
@@ -463,6 +479,10 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     SampleDyn* dyn = (SampleDyn*)(((uintptr_t)(jmin_min + 4) + 15) & ~(uintptr_t)15);
     c->h_dyn.seed = sp->seed; c->h_dyn.temperature = sp->temperature; c->h_dyn.top_k = sp->top_k; c->h_dyn.top_p = sp->top_p;
     HIPCHK(c, hipMemcpyAsync(dyn, &c->h_dyn, sizeof(SampleDyn), hipMemcpyHostToDevice, st));
+    // row mode: the whole table in image order; chain g's sampler reads its slice at rows_dev + img0[g].  The values live in device memory, so a call with
+    // other per-row values replays the captured graph.
+    if (rows && rows_upload(c, rows, B, st)) return -1;
+    const SampleRow* rows_dev = rows ? (const SampleRow*)c->rows_dev.p : nullptr;
     if (emb_mask) car_launch_mask_first_valid((const unsigned char*)c->maskb.p, jmin, b, T, st);
     // ---- prefill window (round 4; SURVEY Appendix E: result-preserving).  Prompts are LEFT-padded (sample_t2i.py:146-160): a pad column is masked for every
     // row of the prefill and for every decode step, so the hidden states and K / V of pad rows influence nothing that is returned — yet the reference (and
@@ -542,6 +562,9 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
             mlp_tanh(c, off(ce, (size_t)img0[gi] * n_tok * D, e), D, 0, 1, (int)rows, D, "condition_layers." + std::to_string(k) + ".", scratch.p,
                      off(c->ctrl[k].p, base * D, e), D, st);
             if (use_cfg) HIPCHK(c, hipMemsetAsync(off(c->ctrl[k].p, (base + rows) * D, e), 0, rows * D * e, st));   // uncond rows: MLP(0) = 0 exactly
+            // row mode: image i's conditional tokens become c' = rnd(cs_i * c) once, here; prefill and decode then add rnd(1 * c') == c' (the unconditional half stays
+            // exact zeros).  Launched only when some row asks for a strength other than 1.
+            if (row_strength) car_launch_ctrl_scale_rows(mode, off(c->ctrl[k].p, base * D, e), rows_dev + img0[gi], ng, (long)n_tok * D, st);
         }
     }
     // ---- E. prefill over the prefix rows of the window [t0, T) (gpt_t2i.py:446-470)
@@ -568,11 +591,13 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     SampleP spp; memset(&spp, 0, sizeof(spp));
     spp.logits = logits; spp.B = B; spp.V = V; spp.use_cfg = use_cfg; spp.cfg_scale = sp->cfg_scale; spp.cfg_interval = sp->cfg_interval;
     spp.step_ptr = step; spp.n_new = n_new; spp.out_tokens = (int*)c->tok_out.p; spp.cur_tok = cur; spp.forced = forced_tokens; spp.logits_out = logits_out;
-    spp.stochastic = sp->sample_logits != 0; spp.temperature = sp->temperature; spp.top_k = sp->top_k; spp.top_p = sp->top_p; spp.seed = sp->seed; spp.row0 = 0;
+    spp.stochastic = ri.any_stochastic; spp.temperature = sp->temperature; spp.top_k = sp->top_k; spp.top_p = sp->top_p; spp.seed = sp->seed; spp.row0 = 0;
     spp.dyn = dyn;     // the sampling scalars live in device memory: changing the seed per call does not invalidate the captured graph
+    if (rows) { spp.dyn = nullptr; spp.rows = rows_dev; spp.cfg_scale = 1.0f; spp.cfg_interval = -1; }      // row mode: every block reads its own row of the device table
     auto group_sampler = [&](int gi) {      // the sampler of group gi: its rows are [cond ng | uncond ng] starting at row mult*img0[gi]
         SampleP q = spp; const int i0 = img0[gi], ng = img0[gi + 1] - i0; const size_t rb = (size_t)mult * i0;
         q.B = ng; q.row0 = i0; q.logits = logits + rb * V; q.out_tokens = (int*)c->tok_out.p + (size_t)i0 * n_new; q.cur_tok = cur + rb;
+        if (rows) { q.rows = rows_dev + i0; q.row0 = 0; }      // the chain's slice of the table; the Philox counter starts at the image's own rng_stream, not at its slot
         q.forced = forced_tokens ? forced_tokens + (size_t)i0 * n_new : nullptr;
         q.logits_out = logits_out ? logits_out + (size_t)i0 * n_new * V : nullptr;
         return q;
@@ -635,12 +660,15 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
         // offsets).  INVARIANT: whatever the step builders read comes from the plan, from a field keyed here, or from the weights — the plan is the schedule and
         // the key, so a switch cannot change the captured kernels without changing the key.
         struct GraphShapes {
-            int b, B, S_max, n_new, n_tok, nsplit, use_control, has_mask, cfg_interval, sample_logits; float cs, cfg_scale; unsigned long long alloc_gen;
-            const void *kv, *h, *xn, *att, *mid, *logits, *ctrl0, *maskb, *parts, *scal, *forced, *logits_out;
+            int b, B, S_max, n_new, n_tok, nsplit, use_control, has_mask, cfg_interval, sample_logits, row_mode; float cs, cfg_scale; unsigned long long alloc_gen;
+            const void *kv, *h, *xn, *att, *mid, *logits, *ctrl0, *maskb, *parts, *scal, *forced, *logits_out, *rows;
         } gs;
         memset(&gs, 0, sizeof(gs));      // (as plan_decode does for the plan: the padding is part of the key)
         gs.b = b; gs.B = B; gs.S_max = S_max; gs.n_new = n_new; gs.n_tok = n_tok; gs.nsplit = nsplit; gs.use_control = use_control; gs.has_mask = emb_mask ? 1 : 0;
-        gs.cfg_interval = sp->cfg_interval; gs.sample_logits = sp->sample_logits; gs.cs = cs; gs.cfg_scale = sp->cfg_scale; gs.alloc_gen = g_alloc_gen;
+        // sample_logits: the KIND of sampler kernel the step launches (car_launch_sample_greedy: stochastic when any row is).  Row mode: scale, interval and strength
+        // live in the device table (the kernels get cs = 1), so they do not distinguish graphs — other per-row values replay the capture
+        gs.cfg_interval = spp.cfg_interval; gs.sample_logits = spp.stochastic; gs.cs = cs; gs.cfg_scale = spp.cfg_scale; gs.row_mode = rows ? 1 : 0; gs.rows = rows_dev;
+        gs.alloc_gen = g_alloc_gen;
         gs.kv = c->kv.p; gs.h = h; gs.xn = xn; gs.att = att; gs.mid = mid; gs.logits = logits; gs.ctrl0 = c->ctrl[0].p; gs.maskb = c->maskb.p;
         gs.parts = c->dec_parts.p ? c->dec_parts.p : c->ws[10].p; gs.scal = c->scal.p; gs.forced = forced_tokens; gs.logits_out = logits_out;
         std::string key((const char*)&pl, sizeof(pl)); key.append((const char*)&gs, sizeof(gs));

@@ -75,7 +75,9 @@ void car_launch_conv_in3(int mode, const float* img, const void* w, const void* 
 void car_launch_vq_argmin(int mode, const void* z, const float* cb, int* tok, long npix, int cd, int ncode, hipStream_t st);
 void car_launch_conv_out(int mode, const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C, hipStream_t st);
 void car_launch_swiglu(int mode, const void* in, void* out, long rows, int hidden, hipStream_t st);
-void car_launch_sample_greedy(const SampleP* p, hipStream_t st);
+int car_launch_sample_greedy(const SampleP* p, hipStream_t st);      // returns the kernel it launched: 1 stochastic, 0 greedy
+void car_launch_ctrl_scale_rows(int mode, void* ctrl, const SampleRow* rows, int n_img, long per, hipStream_t st);
+void car_launch_row_mix_scale(const SampleRow* rows, float* out, int n_img, int n_new, hipStream_t st);
 void car_launch_advance(int* pos, int* step, hipStream_t st);
 void car_launch_set_pos_step(int* dst, int pos, int step, hipStream_t st);
 void car_launch_transpose_pad(int mode, const void* src, long ld, long sb, void* dst, int B, int Tn, int Tpad, int C, hipStream_t st);
@@ -148,6 +150,8 @@ struct car_ctx {
     int h_init[16] = {};
     int h_init2[16] = {};     // the chains' (pos, step) scalars at the switch from the early one-chain schedule to the main one (exact mode)
     SampleDyn h_dyn = {};
+    std::vector<SampleRow> h_rows; DevBuf rows_dev;   // row mode (car_*_rows): the call's row table, host staging (the source of the asynchronous upload) and device copy; the captured decode graph reads the device copy
+    DevBuf row_scale;    // car_score_rows: fp32 [B, n_new], the CFG mix scale of every (image, position) built on the device from the row table (ScoreP::scale)
     int dbg_skip = 0;
     int knob_hits = 0;      // development build: CAR_* switches found set while the last generate was enqueued (car_stats.dev_knobs_active)
     int n_cu = 256;       // compute units of the device (persistent-grid sizing)
@@ -197,6 +201,33 @@ static inline int check_sticky(car_ctx* c) {
 #define NEED(ctx, buf, bytes) do { if (!(buf).ensure(bytes)) FAIL(ctx, "out of device memory allocating %zu bytes (%s:%d)", (size_t)(bytes), __FILE__, __LINE__); } while (0)
 
 static inline size_t rup(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ------------------------------------------------------------------------------------- row mode (car_*_rows): one car_sampling_row per image
+static_assert(sizeof(car_sampling_row) == sizeof(SampleRow) && sizeof(car_sampling_row) == 40, "car_sampling_row and its device image share one layout");
+struct RowInfo { bool use_cfg, any_stochastic; };
+// Host-side validation of the caller's table; `what` names the entry in the message.  Nothing is enqueued and the context stays usable after a refusal.
+static inline int rows_check(car_ctx* c, const char* what, const car_sampling_row* rows, int B, int vocab, RowInfo* ri) {
+    ri->use_cfg = rows[0].cfg_scale > 1.0f; ri->any_stochastic = false;
+    for (int i = 0; i < B; ++i) {
+        const car_sampling_row& r = rows[i];
+        if ((r.cfg_scale > 1.0f) != ri->use_cfg)
+            FAIL(c, "%s: rows 0 and %d disagree about cfg_scale > 1 (%g, %g): the CFG batch doubling is call-wide, so the rows of one call must either all have "
+                    "cfg_scale > 1 or all have cfg_scale <= 1 (u + (c - u) * 1 is not c in fp32: a row at scale 1 inside a CFG batch could not reproduce its plain call)",
+                 what, i, (double)rows[0].cfg_scale, (double)r.cfg_scale);
+        if (r.top_k < 0) FAIL(c, "%s: row %d: top_k must be >= 0 (got %d)", what, i, r.top_k);
+        if (!(r.top_p > 0.0f && r.top_p <= 1.0f)) FAIL(c, "%s: row %d: top_p must be in (0, 1] (got %g)", what, i, (double)r.top_p);
+        if (r.sample_logits) ri->any_stochastic = true;
+    }
+    if (ri->any_stochastic && vocab > 32768) FAIL(c, "%s: stochastic sampling supports vocab_size <= 32768", what);
+    return 0;
+}
+// Copies the table into the context's staging and uploads it on the library stream, the way h_dyn travels; a captured decode graph keeps reading rows_dev.
+static inline int rows_upload(car_ctx* c, const car_sampling_row* rows, int B, hipStream_t st) {
+    c->h_rows.resize((size_t)B); memcpy(c->h_rows.data(), rows, (size_t)B * sizeof(SampleRow));
+    NEED(c, c->rows_dev, (size_t)B * sizeof(SampleRow));
+    HIPCHK(c, hipMemcpyAsync(c->rows_dev.p, c->h_rows.data(), (size_t)B * sizeof(SampleRow), hipMemcpyHostToDevice, st));
+    return 0;
+}
 
 
 // ------------------------------------------------------------------------------------- shared helpers

@@ -37,6 +37,14 @@ static int ensure_host_flags(car_ctx* c) {
 
 extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask, int32_t B, int32_t n_new, int32_t use_control,
                          const car_sampling* sp, const int32_t* tokens, float* nll_out, float* logits_out, void* stream_) {
+    return car_score_rows(c, text_emb, text_dtype, emb_mask, B, n_new, use_control, sp, nullptr, tokens, nll_out, logits_out, stream_);
+}
+
+// Row mode (trows != NULL): image i is scored under its own cfg_scale, cfg_interval and control_strength.  The projection kernel already mixes with a per-row
+// scale (ScoreP::scale, the pair_scale plumbing of car_debug_score_rows): the table's scale / interval become one fp32 per (image, position) on the device.  The
+// strength is folded into the image's control tokens after stage C, as in car_generate_rows, and the pass runs at cs = 1.  A chunk takes its slice of both.
+extern "C" int car_score_rows(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask, int32_t B, int32_t n_new, int32_t use_control,
+                              const car_sampling* sp, const car_sampling_row* trows, const int32_t* tokens, float* nll_out, float* logits_out, void* stream_) {
     if (!c) return -1;
     if (check_sticky(c)) return -1;
     if (c->cfg.model_type != 0) FAIL(c, "car_score: context was created for the c2i model; scoring covers the t2i model only");
@@ -49,9 +57,13 @@ extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     const int T = g.cls_token_num;
     if (n_new > g.block_size) FAIL(c, "car_score: %d tokens exceed block_size %d (rope table rows, gpt_t2i.py:454)", n_new, g.block_size);
     if (use_control && (c->ctrl_B != B || c->ctrl_ntok < n_new)) FAIL(c, "car_score: control tokens cached for B=%d n=%d, requested B=%d n_new=%d (call car_encode_control first)", c->ctrl_B, c->ctrl_ntok, B, n_new);
-    const bool use_cfg = sp->cfg_scale > 1.0f;
+    RowInfo ri = {sp->cfg_scale > 1.0f, false};
+    if (trows && rows_check(c, "car_score_rows", trows, B, 0, &ri)) return -1;
+    const bool use_cfg = ri.use_cfg;
     const int mult = use_cfg ? 2 : 1, b = mult * B;
-    const float cs = use_cfg ? sp->control_strength : 1.0f;         // generate.py:87-92: strength ignored when cfg <= 1
+    const float cs = (use_cfg && !trows) ? sp->control_strength : 1.0f;         // generate.py:87-92: strength ignored when cfg <= 1
+    bool row_strength = false;
+    if (trows && use_cfg && use_control) for (int i = 0; i < B; ++i) row_strength |= trows[i].control_strength != 1.0f;
     const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok, li = g.n_layer / 3;
     const int mode = c->mode; const size_t e = c->esz; const bool fast = mode == CAR_BF16;
     if (D != Hn * 64) FAIL(c, "car_score: heads must be 64 wide");
@@ -60,6 +72,16 @@ extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     int* err_flag = c->host_flags + 2;
 
     fence_in(c, caller);
+    const SampleRow* rows_dev = nullptr; const float* row_scale = nullptr;
+    if (trows) {
+        if (rows_upload(c, trows, B, st)) return -1;
+        rows_dev = (const SampleRow*)c->rows_dev.p;
+        if (use_cfg) {
+            NEED(c, c->row_scale, (size_t)B * n_new * 4);
+            car_launch_row_mix_scale(rows_dev, (float*)c->row_scale.p, B, n_new, st);
+            row_scale = (const float*)c->row_scale.p;
+        }
+    }
     // ---- the prefill window of car_generate on the valid tail of the left-padded prompts, its start a multiple of 32 (see the chunk rule)
     int Tv = T, t0 = 0;
     if (emb_mask && T > 8 && T % 8 == 0 && (fast || T <= 128)) {
@@ -114,6 +136,7 @@ extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, c
             const int ng = std::min(nc, B - i0); const size_t rows = (size_t)ng * n_tok, base = (size_t)mult * i0 * n_tok;
             mlp_tanh(c, off(ce, (size_t)i0 * n_tok * D, e), D, 0, 1, (int)rows, D, "condition_layers." + std::to_string(k) + ".", scratch, off(c->ctrl[k].p, base * D, e), D, st);
             if (use_cfg) HIPCHK(c, hipMemsetAsync(off(c->ctrl[k].p, (base + rows) * D, e), 0, rows * D * e, st));   // uncond rows: MLP(0) = 0 exactly
+            if (row_strength) car_launch_ctrl_scale_rows(mode, off(c->ctrl[k].p, base * D, e), rows_dev + i0, ng, (long)n_tok * D, st);   // row mode: c' = rnd(cs_i * c), once
         }
     }
     const long per_src = (long)T * g.caption_dim, per = (long)Tv * g.caption_dim; const size_t ib = text_dtype == CAR_DT_BF16 ? 2 : 4;
@@ -154,6 +177,7 @@ extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, c
         p.ldx = D; p.seq_stride = Ts; p.row_off = Tv - 1; p.unc_off = (long)ng * Ts; p.R = ng * n_new; p.V = V; p.D = D; p.rows_per_seq = n_new;
         p.paired = use_cfg ? 1 : 0; p.round_bf16 = fast ? 1 : 0;      // fast mode: the logits are a bf16 linear's output widened to fp32 (gpt_t2i.py:470), as the decode step rounds them
         p.cfg_interval = sp->cfg_interval; p.cfg_scale = sp->cfg_scale;
+        if (row_scale) p.scale = row_scale + (size_t)i0 * n_new;      // row mode: the chunk's slice of the per-(image, position) scales
         if (car_launch_score(mode, &p, nll_out + (size_t)i0 * n_new, err_flag, st)) { rc = -3; break; }
     }
     fence_out(c, caller);

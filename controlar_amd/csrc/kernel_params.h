@@ -37,6 +37,12 @@ struct ScoreP {
 };
 
 struct SampleDyn { unsigned long long seed; float temperature; int top_k; float top_p; int pad; };
+// The device image of car_sampling_row (include/controlar_hip.h): one entry per image of a row-mode call, uploaded as the caller wrote it.
+struct SampleRow {
+    float cfg_scale; int cfg_interval; float temperature; int top_k; float top_p; int sample_logits;
+    unsigned long long seed; float control_strength; unsigned rng_stream;
+};
+static_assert(sizeof(SampleRow) == 40, "SampleRow mirrors car_sampling_row");
 
 // ------------------------------------------------------------------ CFG mix + greedy argmax (generate.py:90,105; :59-74 greedy branch)
 // logits fp32 [b, V] (cond rows [0,B), uncond rows [B,2B)).  One block per image.
@@ -49,6 +55,9 @@ struct SampleP {
     int logits_ks; long logits_stride; int round_bf16;   // logits given as split-K partials [ks][b][V]; bf16 rounding of the sum (gpt_t2i.py:470)
     int stochastic; float temperature; int top_k; float top_p; unsigned long long seed; int row0;   // sample_logits=True path (generate.py:59-74)
     const struct SampleDyn* dyn;    // when set, (seed, temperature, top_k, top_p) are read from device memory: a captured graph stays valid across calls
+    const struct SampleRow* rows;   // row mode (device pointer, one entry per image of this launch): block i takes cfg_scale, cfg_interval, temperature, top_k, top_p,
+                                    // seed and greedy-or-stochastic from rows[i], and draws at the Philox counter (row0 + rows[i].rng_stream, step) instead of (row0 + i, step)
+    int mix_step0;                  // added to *step_ptr in the cfg_interval test only (car_sample_logits: the device step is 0, the caller's step arrives here)
 };
 
 struct FlashP {

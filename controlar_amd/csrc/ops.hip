@@ -769,11 +769,14 @@ __device__ inline void sample_logit4(const SampleP& p, long row, int j, float (&
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = p.round_bf16 ? bf2f(f2bf(a[e])) : a[e];
 }
-__global__ __launch_bounds__(1024) void sample_greedy_kernel(SampleP p) {
+// Row mode (SampleP::rows): ONE image per block, so everything a block reads from its row — the scale and interval behind `mix`, temperature / top_k /
+// top_p behind `filt` and `select_only`, greedy versus stochastic — is uniform across the block, and the barriers inside the greedy reduction, the radix
+// select and the bitonic sort stay legal whatever the rows of a launch hold.  Keep it that way: never let two images share a block.
+//
+// The greedy sampler of image i (the whole block; one barrier): CFG mix, lowest index of the maximum.  sample_greedy_kernel is this body; the stochastic
+// kernel calls it for the greedy rows of a row-mode launch — one body, so a greedy row returns the same bits from either kernel.
+__device__ inline void sample_greedy_block(const SampleP& p, int i, int step, bool mix, float cfg_scale) {
     __shared__ float smv[16]; __shared__ int smi[16];
-    const int i = blockIdx.x, step = *p.step_ptr;
-    // cfg_flag of decode_n_tokens: loop index = step-1; flag drops once (step-1) > cfg_interval
-    const bool mix = p.use_cfg && !(p.cfg_interval > -1 && (step - 1) > p.cfg_interval);
     float best = -INFINITY; int bi = 0x7fffffff;
     float* lo = p.logits_out ? p.logits_out + ((long)i * p.n_new + step) * p.V : nullptr;
     for (int j = threadIdx.x * 4; j < p.V; j += blockDim.x * 4) {
@@ -781,7 +784,7 @@ __global__ __launch_bounds__(1024) void sample_greedy_kernel(SampleP p) {
         if (mix) {
             float u[4]; sample_logit4(p, i + p.B, j, u);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = u[e] + (v[e] - u[e]) * p.cfg_scale;
+            for (int e = 0; e < 4; ++e) v[e] = u[e] + (v[e] - u[e]) * cfg_scale;
         }
         if (lo) *(float4*)(lo + j) = make_float4(v[0], v[1], v[2], v[3]);
 #pragma unroll
@@ -803,9 +806,17 @@ __global__ __launch_bounds__(1024) void sample_greedy_kernel(SampleP p) {
         if (p.use_cfg) p.cur_tok[i + p.B] = fb;
     }
 }
+__global__ __launch_bounds__(1024) void sample_greedy_kernel(SampleP p) {
+    const int i = blockIdx.x, step = *p.step_ptr;
+    if (p.rows) { p.cfg_scale = p.rows[i].cfg_scale; p.cfg_interval = p.rows[i].cfg_interval; }      // block-uniform: one image per block
+    // cfg_flag of decode_n_tokens: loop index = step-1; flag drops once (step-1) > cfg_interval
+    const bool mix = p.use_cfg && !(p.cfg_interval > -1 && (step + p.mix_step0 - 1) > p.cfg_interval);
+    sample_greedy_block(p, i, step, mix, p.cfg_scale);
+}
 // ---- stochastic sampling (generate.py:17-74): temperature, top-k (k-th value threshold), top-p (nucleus on the sorted softmax),
 // softmax, multinomial(1).  One 1024-thread block per image; the sorted copy lives in LDS (bitonic sort, descending).
 // RNG: Philox4x32-10 keyed by the caller's seed, counter = (global image row, step): reproducible and order-independent.
+// Row mode: keyed by the image's own seed, counter = (the image's own rng_stream, step) — nothing of the draw depends on the image's slot or on its batch-mates.
 // Ties: filtering is by VALUE threshold (logits >= k-th / nucleus-cut value are kept), which equals the reference's
 // index-based removal whenever the boundary values are distinct.
 __device__ inline void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0, unsigned k1) {
@@ -836,7 +847,15 @@ __global__ __launch_bounds__(1024) void sample_stochastic_kernel(SampleP p, int 
     __shared__ float sm[40]; __shared__ int cut_s; __shared__ int tok_s;
     const int i = blockIdx.x, step = *p.step_ptr, tid = threadIdx.x, nt = blockDim.x;
     if (p.dyn) { p.seed = p.dyn->seed; p.temperature = p.dyn->temperature; p.top_k = p.dyn->top_k; p.top_p = p.dyn->top_p; }
-    const bool mix = p.use_cfg && !(p.cfg_interval > -1 && (step - 1) > p.cfg_interval);
+    unsigned rng_a = (unsigned)(p.row0 + i);      // first word of the Philox counter: the image's index in the batch, or in row mode the image's own stream
+    bool greedy_row = false;
+    if (p.rows) {      // the image's own parameters; every branch below that depends on them is uniform across the block (see sample_greedy_block)
+        const SampleRow r = p.rows[i];
+        p.cfg_scale = r.cfg_scale; p.cfg_interval = r.cfg_interval; p.seed = r.seed; p.temperature = r.temperature; p.top_k = r.top_k; p.top_p = r.top_p;
+        rng_a = (unsigned)p.row0 + r.rng_stream; greedy_row = r.sample_logits == 0;
+    }
+    const bool mix = p.use_cfg && !(p.cfg_interval > -1 && (step + p.mix_step0 - 1) > p.cfg_interval);
+    if (greedy_row) { sample_greedy_block(p, i, step, mix, p.cfg_scale); return; }      // before the first barrier of this kernel
     const float invT = 1.0f / fmaxf(p.temperature, 1e-5f);
     float* lo = p.logits_out ? p.logits_out + ((long)i * p.n_new + step) * p.V : nullptr;
     auto mixed4 = [&](int j, float (&v)[4]) {
@@ -933,7 +952,7 @@ __global__ __launch_bounds__(1024) void sample_stochastic_kernel(SampleP p, int 
         for (int e = 0; e < 4; ++e) { const float x = v[e] * invT; if (x >= thr) loc += expf(x - mx); }
     }
     float total; const float excl = block_excl_scan(loc, sm, total);
-    const float target = philox_uniform(p.seed, (unsigned)(p.row0 + i), (unsigned)step) * total;
+    const float target = philox_uniform(p.seed, rng_a, (unsigned)step) * total;
     // owner of the draw = the LAST thread with a non-empty chunk whose exclusive prefix is <= target.  (Testing
     // excl <= target < excl + loc per thread can select nobody: the scan's excl(t+1) is not bit-equal to excl(t) + loc(t).)
     // The first non-empty chunk has excl == 0 exactly, so an owner always exists and the token is always in the support.
@@ -965,16 +984,53 @@ __global__ __launch_bounds__(1024) void sample_stochastic_kernel(SampleP p, int 
         if (p.use_cfg) p.cur_tok[i + p.B] = fb;
     }
 }
-extern "C" void car_launch_sample_greedy(const SampleP* p, hipStream_t st) {
+// Launches the sampler of p->B images and returns its kind: 1 = sample_stochastic_kernel (dynamic LDS for the sort keys), 0 = sample_greedy_kernel.  In row
+// mode the caller sets `stochastic` when ANY row of the call is stochastic; the greedy rows of such a launch run the greedy body inside the stochastic kernel.
+extern "C" int car_launch_sample_greedy(const SampleP* p, hipStream_t st) {
     if (p->stochastic) {
         int Vp = 4; while (Vp < p->V) Vp <<= 1;
         static bool attr_set = false;
         if (!attr_set) { (void)hipFuncSetAttribute((const void*)sample_stochastic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024); attr_set = true; }
         hipLaunchKernelGGL(sample_stochastic_kernel, dim3(p->B), dim3(1024), (size_t)Vp * 4, st, *p, Vp);
-        return;
+        return 1;
     }
     int th = p->V / 4; th = ((th + 63) / 64) * 64; if (th > 1024) th = 1024; if (th < 64) th = 64;
     hipLaunchKernelGGL(sample_greedy_kernel, dim3(p->B), dim3(th), 0, st, *p);
+    return 0;
+}
+
+// Row mode: the per-image control strength, applied ONCE to the cached control tokens right after the condition layers.  ctrl [n_img][per] in T (per = n_tok * dim,
+// a multiple of 4); image i becomes c' = rnd(cs_i * c) — the inner product of the statement the passes use on the fly, v = rnd(v + rnd(cs * c)) (rmsnorm_kernel
+// above; decode2.hip's norm prologue and rmsnorm2), rounded to the element type the same way.  The passes then run at cs = 1, where rnd(1 * c') == c' exactly.
+template <typename T>
+__global__ __launch_bounds__(256) void ctrl_scale_rows_kernel(T* ctrl, const SampleRow* rows, long per) {
+    const float cs = rows[blockIdx.y].control_strength;
+    T* base = ctrl + (long)blockIdx.y * per;
+    for (long j = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; j < per; j += (long)gridDim.x * blockDim.x * 4) {
+        float c[4]; ld4<T>(base + j, c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) c[e] = ET<T>::rnd(cs * c[e]);
+        st4<T>(base + j, c);
+    }
+}
+// Row mode of car_score: out[i * n_new + j] = the CFG mix scale of image i at position j — its cfg_scale, or exactly 1 (the conditional row as it is) from
+// position cfg_interval + 2 on, the rule score_kernel applies to the call-wide pair (ScoreP::scale)
+__global__ __launch_bounds__(256) void row_mix_scale_kernel(const SampleRow* rows, float* out, long n, int n_new) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const int i = (int)(idx / n_new), j = (int)(idx - (long)i * n_new);
+    const int ci = rows[i].cfg_interval;
+    out[idx] = (ci > -1 && j - 1 > ci) ? 1.f : rows[i].cfg_scale;
+}
+extern "C" void car_launch_row_mix_scale(const SampleRow* rows, float* out, int n_img, int n_new, hipStream_t st) {
+    const long n = (long)n_img * n_new;
+    if (n > 0) hipLaunchKernelGGL(row_mix_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rows, out, n, n_new);
+}
+extern "C" void car_launch_ctrl_scale_rows(int mode, void* ctrl, const SampleRow* rows, int n_img, long per, hipStream_t st) {
+    if (n_img <= 0 || per <= 0) return;
+    long bx = (per / 4 + 255) / 256; if (bx > 64) bx = 64; if (bx < 1) bx = 1;
+    if (mode == 1) hipLaunchKernelGGL(ctrl_scale_rows_kernel<bf16_t>, dim3((unsigned)bx, n_img), dim3(256), 0, st, (bf16_t*)ctrl, rows, per);
+    else hipLaunchKernelGGL(ctrl_scale_rows_kernel<float>, dim3((unsigned)bx, n_img), dim3(256), 0, st, (float*)ctrl, rows, per);
 }
 
 // step bookkeeping: pos += 1, step += 1 (device-side so a captured hipGraph can be replayed)

@@ -50,6 +50,29 @@ def pad_to_world(G: int, world: int) -> int:
     return (G + world - 1) // world * world
 
 
+def shard_rows(params: dict, G: int, world: int, rank: int) -> dict:
+    """The per-image sampling parameters of rank `rank`'s images (Engine.generate / score keywords: cfg_scale, cfg_interval, control_strength,
+    temperature, top_k, top_p, sample_logits, seed, rng_stream).  `params` maps a keyword to one value for all G requests or to a length-G sequence /
+    1-D tensor; a sequence is cut by the rule that shards the images — shard_slice over the batch padded by pad_to_world, a pad entry repeating the
+    LAST request — and a scalar (or None) passes through.  A request's RNG stream is its own (rng_stream, default 0 per image), never its position in a
+    batch, so a request decodes to the same tokens on whichever rank and beside whichever requests it lands."""
+    idx = [min(i, G - 1) for i in range(G)[shard_slice(G, world, rank)]]
+    idx += [G - 1] * (pad_to_world(G, world) // world - len(idx))
+    out = {}
+    for name, v in params.items():
+        if torch.is_tensor(v) and v.dim() == 1:
+            if v.shape[0] != G:
+                raise ValueError(f"shard_rows: {name} has {v.shape[0]} entries for {G} requests")
+            out[name] = v[torch.tensor(idx, dtype=torch.long, device=v.device)]
+        elif isinstance(v, (list, tuple)):
+            if len(v) != G:
+                raise ValueError(f"shard_rows: {name} has {len(v)} entries for {G} requests")
+            out[name] = [v[i] for i in idx]
+        else:
+            out[name] = v
+    return out
+
+
 def packed_layout(G: int, H: int, W: int, T: int, cap: int):
     """Byte sizes (img bf16 [G,3,H,W], emb bf16 [G,T,cap], mask int64 [G,T]) of the packed input buffer; every section starts 8-byte aligned."""
     n_img, n_emb, n_mask = G * 3 * H * W * 2, G * T * cap * 2, G * T * 8

@@ -39,8 +39,45 @@ def first_valid_position(emb_masks: torch.Tensor) -> int:
     return int(first.min())
 
 
+def _per_image(v):
+    """A per-image argument: a list / tuple or a 1-D tensor -> a Python list; one value for the whole call (a 0-d tensor included) -> None."""
+    if torch.is_tensor(v):
+        return v.tolist() if v.dim() == 1 else None
+    return list(v) if isinstance(v, (list, tuple)) else None
+
+
+def sampling_rows(B: int, rng_stream=None, **params):
+    """The row table of a car_*_rows call, or None for the plain call.  `params`: cfg_scale, cfg_interval, temperature, top_k, top_p, sample_logits, seed,
+    control_strength, each one value for the whole call or one per image (list, tuple or 1-D tensor of length B); rng_stream: None, one value or one
+    per image — the first word of an image's Philox counter, 0 per image unless given, so that a request draws the same numbers wherever it sits in a
+    batch.  All scalars and no rng_stream -> None (the existing entry points, unchanged).  Anything else -> a (CarSamplingRow * B) array with the
+    scalars broadcast.  Raises ValueError, before the library is entered, on a length other than B and on rows that disagree about cfg_scale > 1:
+    the CFG batch doubling is call-wide."""
+    cols = {k: _per_image(v) for k, v in params.items()}
+    streams = _per_image(rng_stream)
+    if rng_stream is None and all(c is None for c in cols.values()):
+        return None
+    for name, c in list(cols.items()) + [("rng_stream", streams)]:
+        if c is not None and len(c) != B:
+            raise ValueError(f"{name} has {len(c)} entries for a batch of {B} images")
+    at = lambda name, i: cols[name][i] if cols[name] is not None else params[name]
+    rows = (L.CarSamplingRow * B)()
+    for i, r in enumerate(rows):
+        r.cfg_scale, r.cfg_interval, r.temperature, r.top_k = float(at("cfg_scale", i)), int(at("cfg_interval", i)), float(at("temperature", i)), int(at("top_k", i) or 0)
+        r.top_p, r.sample_logits, r.seed = float(at("top_p", i)), int(bool(at("sample_logits", i))), int(at("seed", i)) & (2 ** 64 - 1)
+        r.control_strength = float(at("control_strength", i))
+        r.rng_stream = int(streams[i] if streams is not None else (rng_stream or 0)) & (2 ** 32 - 1)
+    over = [r.cfg_scale > 1.0 for r in rows]
+    if any(over) != all(over):
+        raise ValueError("cfg_scale: the rows of one call must either all be > 1 or all be <= 1 (the CFG batch doubling is call-wide; a row at scale 1 "
+                         "inside a CFG batch would compute u + (c - u) * 1, which is not c in fp32)")
+    return rows
+
+
 class Engine:
     """One context = one set of weights in one arithmetic mode ('fp32' exact | 'bf16' fast)."""
+
+    sampling_rows = staticmethod(sampling_rows)
 
     def __init__(self, cfg: PathConfig, precision: str = "bf16", device: Optional[torch.device] = None, stream_priority: int = 0,
                  weights_fp8: bool = False, kv_fp8: bool = False, dev: Optional[bool] = None, vq_split: bool = False):
@@ -158,8 +195,12 @@ class Engine:
     def generate(self, cond: torch.Tensor, max_new_tokens: int, emb_masks: Optional[torch.Tensor] = None,
                  cfg_scale: float = 1.0, cfg_interval: int = -1, use_control: bool = True, control_strength: float = 1.0,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, sample_logits: bool = False, seed: int = 0,
-                 forced_tokens: Optional[torch.Tensor] = None, return_logits: bool = False, first_valid: Optional[int] = None):
-        """`first_valid`: a lower bound of the first valid (unpadded) prompt position over the batch, if the caller knows it — car_generate then sizes its prefill
+                 forced_tokens: Optional[torch.Tensor] = None, return_logits: bool = False, first_valid: Optional[int] = None, rng_stream=None):
+        """cfg_scale, cfg_interval, control_strength, temperature, top_k, top_p, sample_logits and seed each take one value for the call or one per
+        image (a length-B list, tuple or 1-D tensor); with any of them per image, or with `rng_stream` given (one value or one per image; 0 per image
+        otherwise), the call goes through car_generate_rows / car_generate_c2i_rows with the scalars broadcast (sampling_rows above): an image's
+        result is then a function of its own row alone — in the fp32 mode bit for bit, whatever the batch around it.
+        `first_valid`: a lower bound of the first valid (unpadded) prompt position over the batch, if the caller knows it — car_generate then sizes its prefill
         window without reading the device mask back (no host wait).  A mask that is still on the host supplies it for free, and a caller-supplied value is
         checked against such a mask here.  With a DEVICE mask a value that is too large cannot be seen without the host wait the hint exists to avoid: the
         device raises a sticky error flag, and it surfaces at the NEXT entry into the context, at stats(), check_errors() or close() — the tokens of the
@@ -190,16 +231,32 @@ class Engine:
                 if first_valid is None:
                     first_valid = true_first
             mask_t = emb_masks.to(device=self.device, dtype=torch.int64).contiguous()
+        rows = sampling_rows(B, rng_stream, cfg_scale=cfg_scale, cfg_interval=cfg_interval, temperature=temperature, top_k=top_k, top_p=top_p,
+                             sample_logits=sample_logits, seed=seed, control_strength=control_strength)
         sp = L.CarSampling()
         sp.first_valid_hint = 0 if (first_valid is None or emb_masks is None) else max(0, min(int(first_valid), T)) + 1
-        sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), float(temperature), int(top_k or 0)
-        sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = float(top_p), int(bool(sample_logits)), int(seed), float(control_strength)
+        if rows is None:
+            sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), float(temperature), int(top_k or 0)
+            sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = float(top_p), int(bool(sample_logits)), int(seed), float(control_strength)
         out = torch.empty(B, max_new_tokens, dtype=torch.int32, device=self.device)
         forced = None
         if forced_tokens is not None:
             forced = forced_tokens.to(device=self.device, dtype=torch.int32).contiguous()
         logits = torch.empty(B, max_new_tokens, self.cfg.gpt.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
-        if c2i:
+        if rows is not None and c2i:
+            self._check(self.lib.car_generate_c2i_rows(self._h, C.c_void_p(cond.data_ptr()), B, int(max_new_tokens), int(bool(use_control)),
+                                                       C.byref(sp), rows, C.c_void_p(out.data_ptr()),
+                                                       C.c_void_p(forced.data_ptr() if forced is not None else 0),
+                                                       C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())),
+                        "car_generate_c2i_rows")
+        elif rows is not None:
+            self._check(self.lib.car_generate_rows(self._h, C.c_void_p(cond.data_ptr()), _dt(cond),
+                                                   C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0), B, int(max_new_tokens),
+                                                   int(bool(use_control)), C.byref(sp), rows, C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(forced.data_ptr() if forced is not None else 0),
+                                                   C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())),
+                        "car_generate_rows")
+        elif c2i:
             self._check(self.lib.car_generate_c2i(self._h, C.c_void_p(cond.data_ptr()), B, int(max_new_tokens), int(bool(use_control)),
                                                   C.byref(sp), C.c_void_p(out.data_ptr()),
                                                   C.c_void_p(forced.data_ptr() if forced is not None else 0),
@@ -220,7 +277,7 @@ class Engine:
         """Per-token negative log-likelihood of `tokens` [B,N] under the prompt `cond` (and the control of the preceding encode_control) in one parallel
         pass (car_score): nll[b,i] = logsumexp(l_i) - l_i[tokens[b,i]] with l_i the logits row generate() would sample step i from after feeding back
         tokens[b,:i] (after the CFG mix, before temperature / top-k / top-p).  Returns fp32 [B,N], or (nll, logits [B,N,V]) with return_logits.  The other
-        arguments mean what they mean to generate().  A token id outside [0, vocab) on a host tensor raises here; on a device tensor it raises the sticky
+        arguments mean what they mean to generate(); cfg_scale, cfg_interval and control_strength may be given per image (car_score_rows).  A token id outside [0, vocab) on a host tensor raises here; on a device tensor it raises the sticky
         flag (check_errors)."""
         if self.cfg.gpt.model_type == "c2i":
             raise RuntimeError("car_score: context was created for the c2i model; scoring covers the t2i model only")
@@ -250,13 +307,21 @@ class Engine:
                 if first_valid is None:
                     first_valid = true_first
             mask_t = emb_masks.to(device=self.device, dtype=torch.int64).contiguous()
+        rows = sampling_rows(B, None, cfg_scale=cfg_scale, cfg_interval=cfg_interval, temperature=1.0, top_k=0, top_p=1.0, sample_logits=False, seed=0,
+                             control_strength=control_strength)
         sp = L.CarSampling()
         sp.first_valid_hint = 0 if (first_valid is None or emb_masks is None) else max(0, min(int(first_valid), T)) + 1
-        sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), 1.0, 0
-        sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = 1.0, 0, 0, float(control_strength)
+        if rows is None:
+            sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), 1.0, 0
+            sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = 1.0, 0, 0, float(control_strength)
         tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
         nll = torch.empty(B, N, dtype=torch.float32, device=self.device)
         logits = torch.empty(B, N, self.cfg.gpt.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
+        if rows is not None:
+            self._check(self.lib.car_score_rows(self._h, C.c_void_p(cond.data_ptr()), _dt(cond), C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0),
+                                                B, N, int(bool(use_control)), C.byref(sp), rows, C.c_void_p(tok.data_ptr()), C.c_void_p(nll.data_ptr()),
+                                                C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())), "car_score_rows")
+            return (nll, logits) if return_logits else nll
         self._check(self.lib.car_score(self._h, C.c_void_p(cond.data_ptr()), _dt(cond), C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0),
                                        B, N, int(bool(use_control)), C.byref(sp), C.c_void_p(tok.data_ptr()), C.c_void_p(nll.data_ptr()),
                                        C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())), "car_score")
@@ -288,15 +353,24 @@ class Engine:
         return (nll, logits) if return_logits else nll
 
     def sample(self, logits: torch.Tensor, cfg_scale: float = 1.0, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-               sample_logits: bool = True, seed: int = 0, step: int = 0) -> torch.Tensor:
-        """generate.py:59-74 sample() on caller-provided fp32 logits [rows, V] (rows = 2B under CFG) -> int32 [B]."""
+               sample_logits: bool = True, seed: int = 0, step: int = 0, cfg_interval: int = -1, rng_stream=None) -> torch.Tensor:
+        """generate.py:59-74 sample() on caller-provided fp32 logits [rows, V] (rows = 2B under CFG) -> int32 [B].  Every sampling argument takes one
+        value or one per image, and `rng_stream` one value or one per image, as in generate(): car_sample_logits_rows.  `step` stands for the loop
+        index + 1 of the token loop: the CFG mix is dropped where cfg_interval > -1 and step - 1 > cfg_interval."""
         logits = logits.to(device=self.device, dtype=torch.float32).contiguous()
         rows, V = logits.shape
-        B = rows // 2 if cfg_scale > 1.0 else rows
+        scales = _per_image(cfg_scale)
+        B = rows // 2 if (scales[0] if scales else cfg_scale) > 1.0 else rows
+        tab = sampling_rows(B, rng_stream, cfg_scale=cfg_scale, cfg_interval=cfg_interval, temperature=temperature, top_k=top_k, top_p=top_p,
+                            sample_logits=sample_logits, seed=seed, control_strength=1.0)
         sp = L.CarSampling()
-        sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), -1, float(temperature), int(top_k or 0)
-        sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = float(top_p), int(bool(sample_logits)), int(seed), 1.0
         out = torch.empty(B, dtype=torch.int32, device=self.device)
+        if tab is not None:
+            self._check(self.lib.car_sample_logits_rows(self._h, C.c_void_p(logits.data_ptr()), B, V, C.byref(sp), tab, int(step),
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())), "car_sample_logits_rows")
+            return out
+        sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), float(temperature), int(top_k or 0)
+        sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = float(top_p), int(bool(sample_logits)), int(seed), 1.0
         self._check(self.lib.car_sample_logits(self._h, C.c_void_p(logits.data_ptr()), B, V, C.byref(sp), int(step),
                                                C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())), "car_sample_logits")
         return out

@@ -13,15 +13,24 @@ def _call_seed(kw) -> int:
     (torch.multinomial, generate.py:72), so consecutive calls differ and torch.manual_seed() reproduces a run; the same holds
     here: without an explicit `seed` kwarg (an extension) one 62-bit value is drawn from torch's CPU generator per call."""
     if "seed" in kw and kw["seed"] is not None:
-        return int(kw["seed"])
+        return _arg(kw["seed"], int)
     return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def _arg(v, cast):
+    """One value for the call -> cast(v); one value per image (list, tuple, 1-D tensor) -> passed through for Engine's row table."""
+    if isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() == 1):
+        return v
+    return cast(v)
 
 
 @torch.no_grad()
 def generate(model: Transformer, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, condition=None,
              condition_null=None, condition_token_nums=0, control_strength=1, **sampling_kwargs):
     """Returns int32 [B, max_new_tokens] on cond.device.  sampling_kwargs: temperature, top_k (default 2000 as sample(),
-    generate.py:59), top_p, sample_logits (default True).  `condition` is the control image [B,3,H,W] in [-1,1] (or None)."""
+    generate.py:59), top_p, sample_logits (default True), and the extensions seed and rng_stream.  `condition` is the control image [B,3,H,W] in
+    [-1,1] (or None).  cfg_scale, cfg_interval, control_strength and every sampling kwarg may be one value or one per image (list, tuple or 1-D tensor
+    of length B): Engine.generate then takes the row-table entry (car_generate_rows)."""
     if model.model_type not in ("t2i", "c2i"):
         raise Exception("please check model type")
     eng = model.engine
@@ -34,11 +43,11 @@ def generate(model: Transformer, cond, max_new_tokens, emb_masks=None, cfg_scale
         assert emb_masks.shape[-1] == (1 + condition_token_nums if model.model_type == "c2i" else cond.shape[1])
     if model.model_type == "c2i" and condition_token_nums != 0:
         raise RuntimeError("c2i: condition_token_nums must be 0 (the only value the reference samplers pass, sample_c2i.py:55)")
-    out = eng.generate(cond, int(max_new_tokens), emb_masks, cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval),
-                       use_control=condition is not None, control_strength=float(control_strength),
-                       temperature=float(sampling_kwargs.get("temperature", 1.0)), top_k=int(sampling_kwargs.get("top_k", 2000) or 0),
-                       top_p=float(sampling_kwargs.get("top_p", 1.0)), sample_logits=bool(sampling_kwargs.get("sample_logits", True)),
-                       seed=_call_seed(sampling_kwargs))
+    out = eng.generate(cond, int(max_new_tokens), emb_masks, cfg_scale=_arg(cfg_scale, float), cfg_interval=_arg(cfg_interval, int),
+                       use_control=condition is not None, control_strength=_arg(control_strength, float),
+                       temperature=_arg(sampling_kwargs.get("temperature", 1.0), float), top_k=_arg(sampling_kwargs.get("top_k", 2000), lambda k: int(k or 0)),
+                       top_p=_arg(sampling_kwargs.get("top_p", 1.0), float), sample_logits=_arg(sampling_kwargs.get("sample_logits", True), bool),
+                       seed=_call_seed(sampling_kwargs), rng_stream=sampling_kwargs.get("rng_stream"))
     return out.to(cond.device)
 
 
@@ -68,7 +77,7 @@ def score(model: Transformer, cond, tokens, emb_masks=None, cfg_scale=1.0, cfg_i
         eng.encode_control(condition)                       # model.adapter + model.adapter_mlp (generate.py:136-138)
     if emb_masks is not None:
         assert emb_masks.shape[0] == cond.shape[0] and emb_masks.shape[-1] == cond.shape[1]          # generate.py:185-186
-    nll = eng.score(cond, tokens, emb_masks, cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval), use_control=condition is not None,
-                    control_strength=float(control_strength))
+    nll = eng.score(cond, tokens, emb_masks, cfg_scale=_arg(cfg_scale, float), cfg_interval=_arg(cfg_interval, int), use_control=condition is not None,
+                    control_strength=_arg(control_strength, float))
     loss = score_loss(nll, valid)
     return nll.to(cond.device), loss.to(cond.device)

@@ -101,6 +101,22 @@ typedef struct car_sampling {
     int32_t  reserved[3];
 } car_sampling;
 
+/* sampling parameters of ONE image of a batch: the per-request form of the fields above, for the *_rows entry points below (40 bytes).  Every image carries
+ * its own parameters and its own RNG stream, so its result is a function of its own row alone: it does not change with the slot it occupies, with the
+ * requests beside it, or with the rank a shard of the batch runs on — in the CAR_F32 mode bit for bit (that mode is batch-invariant by construction). */
+typedef struct car_sampling_row {
+    float    cfg_scale;        /* the rows of one call are all > 1 or all <= 1: the CFG batch doubling is call-wide */
+    int32_t  cfg_interval;
+    float    temperature;
+    int32_t  top_k;            /* >= 0 */
+    float    top_p;            /* in (0, 1] */
+    int32_t  sample_logits;    /* greedy and stochastic rows may share a call */
+    uint64_t seed;
+    float    control_strength; /* ignored (= 1) when the call is not under CFG, and in c2i */
+    uint32_t rng_stream;       /* first word of this image's Philox counter: (rng_stream, step).  The plain entry points use the image's index in the batch; a
+                                  request that is to be replayed, re-batched or moved to another rank keeps one value (0 is fine: the seed tells requests apart) */
+} car_sampling_row;
+
 typedef struct car_ctx car_ctx;
 
 /* lifecycle */
@@ -427,10 +443,36 @@ int car_generate_c2i(car_ctx* ctx, const int64_t* labels, int32_t B, int32_t n_n
  * sample() — autoregressive/models/generate.py:59-74 (with top_k_top_p_filtering :17-56) on caller-provided logits:
  * logits fp32 [rows, V] with rows = B, or 2B under CFG (cond rows then uncond rows, mixed as generate.py:105);
  * greedy (sample_logits = 0) or temperature / top-k / top-p / multinomial with a Philox counter RNG keyed by
- * (seed, image row, step).  out int32 [B] (device).  The same kernels run inside car_generate's token loop.
+ * (seed, image row, step).  out int32 [B] (device).  The same kernels run inside car_generate's token loop.  `step` is the index of the token being
+ * sampled, as in that loop: with cfg_interval > -1 the mix is dropped where step - 1 > cfg_interval (generate.py:121-122).
  */
 int car_sample_logits(car_ctx* ctx, const float* logits, int32_t B, int32_t V, const car_sampling* sp, int32_t step,
                       int32_t* out, void* stream);
+
+/*
+ * Per-request sampling parameters inside one batch: the four entries above with a row table behind `sp`.  rows: a HOST array of B car_sampling_row, one per
+ * image, copied before the call returns.  With rows != NULL only the call-wide field of `sp` is read (first_valid_hint); with rows == NULL each is the
+ * entry it is named after.  Image i mixes with its own cfg_scale and cfg_interval, filters with its own temperature / top_k / top_p, is greedy or stochastic
+ * by its own sample_logits, and draws from Philox keyed by its own seed at counter (rng_stream, step); car_sample_logits_rows draws at
+ * (step * 65536 + rng_stream, 0), as the plain entry does with the image index.  control_strength of image i scales its control tokens once, in the
+ * element type, right after the condition layers (c' = rnd(cs_i * c), the product the plain call forms inside its kernels), and the passes then run at
+ * strength 1; it is ignored where the plain call ignores it.  forced_tokens and logits_out work as in the plain calls; logits_out holds each image's own
+ * mixed logits.  car_score_rows reads cfg_scale, cfg_interval and control_strength of each row.  The table lives in device memory that the captured decode
+ * graph references: a second call with other values replays the graph.
+ * Refused on the host, with the context left usable: rows that disagree about cfg_scale > 1 (the CFG batch doubling is call-wide, and u + (c - u) * 1 is
+ * not c in fp32, so a row at scale 1 inside a CFG batch could not reproduce its plain call); top_k < 0; top_p outside (0, 1]; vocab_size > 32768 when any
+ * row is stochastic.
+ */
+int car_generate_rows(car_ctx* ctx, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask,
+                      int32_t B, int32_t n_new, int32_t use_control, const car_sampling* sp, const car_sampling_row* rows,
+                      int32_t* out_tokens, const int32_t* forced_tokens, float* logits_out, void* stream);
+int car_generate_c2i_rows(car_ctx* ctx, const int64_t* labels, int32_t B, int32_t n_new, int32_t use_control, const car_sampling* sp,
+                          const car_sampling_row* rows, int32_t* out_tokens, const int32_t* forced_tokens, float* logits_out, void* stream);
+int car_score_rows(car_ctx* ctx, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask,
+                   int32_t B, int32_t n_new, int32_t use_control, const car_sampling* sp, const car_sampling_row* rows,
+                   const int32_t* tokens, float* nll_out, float* logits_out, void* stream);
+int car_sample_logits_rows(car_ctx* ctx, const float* logits, int32_t B, int32_t V, const car_sampling* sp, const car_sampling_row* rows,
+                           int32_t step, int32_t* out, void* stream);
 
 /*
  * VQModel.decode_code(code_b, [B,C,h,w], channel_first=True) — tokenizer/tokenizer_image/vq_model.py:53-56.
