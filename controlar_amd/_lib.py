@@ -19,6 +19,8 @@ CAR_ABI_VERSION = 2
 CAR_F32, CAR_BF16 = 0, 1
 CAR_DT_F32, CAR_DT_BF16, CAR_DT_I32, CAR_DT_I64, CAR_DT_U8 = 0, 1, 2, 3, 4
 CAR_RESIZE_NEAREST, CAR_RESIZE_BICUBIC_AC = 0, 1
+# car_psnr: how an element is read before the difference
+CAR_PSNR_RAW, CAR_PSNR_DIV255, CAR_PSNR_HALF = 0, 1, 2
 # car_resize filters: Pillow's own codes (Image.Resampling)
 CAR_FILTER_LANCZOS, CAR_FILTER_BILINEAR, CAR_FILTER_BICUBIC, CAR_FILTER_BOX, CAR_FILTER_HAMMING = 1, 2, 3, 4, 5
 
@@ -134,6 +136,12 @@ SYMBOLS = {
                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_rmse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "car_pixels_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_lpips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "car_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_void_p,
+                           C.c_void_p]),
+    "car_recon_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "car_debug_lpips_canonical_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32]),
+    "car_debug_lpips_chunk_pairs": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "car_lineart": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_hed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "car_depth_configure": (C.c_int, [C.c_void_p, C.POINTER(CarDptConfig)]),

@@ -2,7 +2,7 @@
 // packing, finalize, the packed-image cache; engine_attn.hip: the batched multi-head attention every transformer stage calls (attn_bytes / attn_run) and the
 // GPT layer tail shared by the prefill and car_score; engine_encode.hip: resize tables, the control encoder, Canny; engine_generate.hip: prefill, the decode
 // step, generate; engine_score.hip: car_score; engine_t5.hip: the caption encoder; engine_clip.hip: the CLIP score; engine_vq.hip: VQ encode / decode;
-// engine_depth.hip, engine_hed.hip, engine_lineart.hip: the control extractors; engine_resize.hip, engine_metrics.hip).  Round 4 cut the single 1900-line
+// engine_depth.hip, engine_hed.hip, engine_lineart.hip: the control extractors; engine_lpips.hip: LPIPS, PSNR and the tokenizer script's quantiser; engine_resize.hip, engine_metrics.hip).  Round 4 cut the single 1900-line
 // engine.hip along its stage banners: no behaviour change.  Everything here is internal: the C ABI is include/controlar_hip.h.
 #pragma once
 #include "car_common.h"
@@ -161,6 +161,7 @@ struct car_ctx {
                                  // with a system-scope store, and every entry that takes this context reads it without a host wait (check_sticky)
     DevBuf canny_map;    // car_canny: uint8 [B,H,W] candidate/edge map + the "changed" flag
     DevBuf lineart_ws;   // car_lineart: NHWC activations, raw fp32 conv outputs and InstanceNorm partials of one chunk of images (grows on demand)
+    DevBuf lpips_ws;     // car_lpips: NHWC activations (two rotating buffers) of both images and the head partials of one chunk of pairs (grows on demand)
     DevBuf hed_ws;       // car_hed: NHWC activations (two rotating buffers) and the side-output partials of one chunk of images (grows on demand)
     car_dpt_config dpt = {}; bool has_dpt = false;   // car_depth_configure
     std::map<int, void*> depth_pos_cache;   // token grid -> T [1 + g*g, hidden]: depth.dpt.embeddings.position_embeddings resized bilinearly
@@ -329,13 +330,14 @@ struct LoadedTensor {
     int ndim() const { return (int)shape.size(); }
 };
 // Every model family keeps its loader and the list of tensors car_finalize_weights asks for next to its runner: engine_lineart.hip ("lineart."),
-// engine_hed.hip ("hed."), engine_depth.hip ("depth."), engine_t5.hip ("t5."), engine_clip.hip ("clip."), engine_vq.hip (decoder. / encoder. / quant* / post_quant_conv.),
+// engine_hed.hip ("hed."), engine_lpips.hip ("lpips."), engine_depth.hip ("depth."), engine_t5.hip ("t5."), engine_clip.hip ("clip."), engine_vq.hip (decoder. / encoder. / quant* / post_quant_conv.),
 // engine_weights.hip (the GPT and its ViT adapter).  A name list holds what the loaders leave in car_ctx::w (host_keep for the DPT position table).
 int lineart_load_tensor(car_ctx* c, const LoadedTensor& t);
 int hed_load_tensor(car_ctx* c, const LoadedTensor& t);
 int depth_load_tensor(car_ctx* c, const LoadedTensor& t);
 int t5_load_tensor(car_ctx* c, const LoadedTensor& t);
 int clip_load_tensor(car_ctx* c, const LoadedTensor& t);
+int lpips_load_tensor(car_ctx* c, const LoadedTensor& t);
 int vq_load_tensor(car_ctx* c, const LoadedTensor& t);
 int gpt_load_tensor(car_ctx* c, const LoadedTensor& t);
 void lineart_tensor_names(const car_ctx* c, std::vector<std::string>& v);
@@ -343,6 +345,7 @@ void hed_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void depth_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void t5_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void clip_tensor_names(const car_ctx* c, std::vector<std::string>& v);
+void lpips_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void vq_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 void gpt_tensor_names(const car_ctx* c, std::vector<std::string>& v);
 // engine_weights.hip

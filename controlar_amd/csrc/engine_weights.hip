@@ -246,7 +246,7 @@ extern "C" int car_load_tensor(car_ctx* c, const char* cname, const void* ptr, c
     // every family packs its own tensors, next to its runner; what carries no family's prefix belongs to the GPT or its ViT adapter
     const LoadedTensor t{name, cname, shp, n, h};
     static const struct { const char* prefix; int (*load)(car_ctx*, const LoadedTensor&); } kFamilies[] = {
-        {"lineart.", lineart_load_tensor}, {"hed.", hed_load_tensor}, {"depth.", depth_load_tensor}, {"t5.", t5_load_tensor}, {"clip.", clip_load_tensor},
+        {"lineart.", lineart_load_tensor}, {"hed.", hed_load_tensor}, {"depth.", depth_load_tensor}, {"t5.", t5_load_tensor}, {"clip.", clip_load_tensor}, {"lpips.", lpips_load_tensor},
         {"decoder.", vq_load_tensor}, {"encoder.", vq_load_tensor}, {"quant", vq_load_tensor}, {"post_quant_conv.", vq_load_tensor}};
     for (auto& f : kFamilies) if (starts_with(name, f.prefix)) return f.load(c, t);
     return gpt_load_tensor(c, t);
@@ -275,9 +275,9 @@ extern "C" int car_finalize_weights(car_ctx* c) {
     // a context may serve only decode_code (VQ weights alone) — the reference keeps GPT and VQ as separate modules; the extractors and the caption encoder
     // may be held alone as well
     const bool have_la = group(lineart_tensor_names, true), have_hed = group(hed_tensor_names, true), have_dpt = c->has_dpt && group(depth_tensor_names, true);
-    const bool have_clip = c->has_clip && group(clip_tensor_names, true);
+    const bool have_clip = c->has_clip && group(clip_tensor_names, true), have_lpips = group(lpips_tensor_names, true);
     const bool have_t5 = c->has_t5 && Wp(c, "t5.shared.weight"), have_vq = Wp(c, "quantize.embedding.weight") != nullptr;
-    const bool vq_only = (have_vq || have_t5 || have_la || have_hed || have_dpt || have_clip) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
+    const bool vq_only = (have_vq || have_t5 || have_la || have_hed || have_dpt || have_clip || have_lpips) && !Wp(c, "tok_embeddings.weight") && !Wp(c, "output.weight");
     c->has_gpt = !vq_only;
     auto host_table = [&](const char* r) { if (!have(r)) { miss.names += std::string(r) + " "; ++miss.n; } };      // named even behind six others
     if (have_t5) { group(t5_tensor_names, false); host_table("t5.encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"); }

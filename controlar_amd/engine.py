@@ -541,6 +541,58 @@ class Engine:
                                               C.c_void_p(fl.data_ptr() if fl is not None else 0), C.c_void_p(_stream_ptr())), "car_pixels_to_u8")
         return (out, fl) if want_float else out
 
+    # ------------------------------------------------------------------ reconstruction quality (tokenizer/tokenizer_image/lpips.py, reconstruction_vq_ddp.py)
+    def load_lpips(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
+        """LPIPS().state_dict() names (tokenizer/tokenizer_image/lpips.py:53-65: net.slice1.0.weight ... lin4.model.1.weight, scaling_layer.shift / .scale
+        optional), with the trunk alternatively under torchvision's features.N.weight / .bias (the LPIPS checkpoint holds the lin layers only); the C ABI
+        namespaces them under 'lpips.'.  May be called once per file: finalize=False for all but the last."""
+        self.load_state_dict({"lpips." + k: v for k, v in sd.items()}, finalize=finalize)
+
+    def lpips(self, a: torch.Tensor, b: torch.Tensor, want_layers: bool = False):
+        """LPIPS.forward(a, b) in inference on the GPU (car_lpips).  a, b [B,3,H,W] in [-1,1] -> fp64 [B]; with want_layers also fp64 [B,5], the per-layer
+        terms whose sum in the order 0..4 it is.  Identical inputs give exactly 0; lpips(a, b) and lpips(b, a) are bit-equal."""
+        if a.shape != b.shape:
+            raise ValueError(f"lpips: the images differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+        if a.dim() != 4 or a.shape[1] != 3 or a.numel() == 0:
+            raise ValueError(f"lpips: expected two non-empty image batches [B,3,H,W], got {tuple(a.shape)}")
+        x, y = (t.to(device=self.device, dtype=torch.float32).contiguous() for t in (a, b))
+        B, _, H, W = x.shape
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        lay = torch.empty(B, 5, dtype=torch.float64, device=self.device) if want_layers else None
+        self._check(self.lib.car_lpips(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(lay.data_ptr() if lay is not None else 0), C.c_void_p(_stream_ptr())), "car_lpips")
+        return (out, lay) if want_layers else out
+
+    def psnr(self, a: torch.Tensor, b: torch.Tensor, data_range: float = 1.0, a_map=None, b_map=None) -> torch.Tensor:
+        """skimage's peak_signal_noise_ratio(a, b, data_range=data_range) per image on the GPU (car_psnr): 10 log10(data_range^2 / mse), mse the fp64 mean
+        over everything behind the first axis; +inf for equal images.  a, b [B,...] of one shape, each uint8 or float.  A map reads an element first, in
+        fp32: 'raw' v, 'div255' v / 255, 'half' (v + 1) / 2; default 'div255' for a uint8 input (reconstruction_vq_ddp.py:149) and 'raw' for a float one.
+        Returns fp64 [B]."""
+        if a.shape != b.shape:
+            raise ValueError(f"psnr: the inputs differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+        if a.dim() < 2 or a.numel() == 0:
+            raise ValueError(f"psnr: expected non-empty [B,...], got {tuple(a.shape)}")
+        codes = {"raw": L.CAR_PSNR_RAW, "div255": L.CAR_PSNR_DIV255, "half": L.CAR_PSNR_HALF}
+        x, y = self._metric_input(a, "psnr"), self._metric_input(b, "psnr")
+        mx = codes["div255" if x.dtype == torch.uint8 else "raw"] if a_map is None else codes[a_map]
+        my = codes["div255" if y.dtype == torch.uint8 else "raw"] if b_map is None else codes[b_map]
+        B = x.shape[0]
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        self._check(self.lib.car_psnr(self._h, C.c_void_p(x.data_ptr()), self._metric_dt(x), mx, C.c_void_p(y.data_ptr()), self._metric_dt(y), my, B,
+                                      x.numel() // B, float(data_range), C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())), "car_psnr")
+        return out
+
+    def recon_to_u8(self, x: torch.Tensor) -> torch.Tensor:
+        """torch.clamp(127.5 * x + 128.0, 0, 255).to(torch.uint8), the quantiser of reconstruction_vq_ddp.py:144 and val_ddp.py:138, bit for bit on the GPU
+        (car_recon_to_u8).  x float, any shape -> uint8 of that shape.  Not save_image's rule: that one is pixels_to_u8."""
+        if x.numel() == 0:
+            raise ValueError(f"recon_to_u8: empty input {tuple(x.shape)}")
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty(x.shape, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.car_recon_to_u8(self._h, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())),
+                    "car_recon_to_u8")
+        return out
+
     def load_lineart(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
         """LineArt().state_dict() names (condition/lineart.py:26-72: model0.1.weight ... model4.1.bias); the C ABI namespaces them under 'lineart.'."""
         self.load_state_dict({"lineart." + k: v for k, v in sd.items()}, finalize=finalize)

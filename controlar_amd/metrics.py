@@ -179,3 +179,80 @@ class CLIPScore:
         if vals.numel() == 0:
             raise ValueError("No images have been added.")
         return float(vals[:self.how_many].to(torch.float64).mean())          # one scalar leaves the device: the script's torch.cat(...)[:how_many].mean()
+
+
+class PSNR(_Accumulator):
+    """PSNR in ``metric.py``'s call shape: ``update(img1, img2)`` adds skimage's ``peak_signal_noise_ratio`` of every image, as the tokenizer evaluation
+    collects it (tokenizer/tokenizer_image/reconstruction_vq_ddp.py:149-153).  img1, img2: [B,...] of one shape, uint8 (read as v / 255) or float in
+    0..data_range.  Equal images give +inf, as skimage does."""
+
+    def __init__(self, data_range=1.0, engine=None, device=None):
+        super().__init__(engine, device)
+        self.data_range = float(data_range)
+
+    def update(self, img1, img2) -> torch.Tensor:
+        return self._add(self._eng.psnr(_t(img1), _t(img2), data_range=self.data_range))
+
+
+class LPIPS(_Accumulator):
+    """The reference's ``LPIPS().eval()`` (tokenizer/tokenizer_image/lpips.py:53-96) as an accumulator: ``update(img1, img2)`` on [B,3,H,W] in [-1,1].
+    ``engine`` holds the weights (``Engine.load_lpips``), or ``weights`` (a local checkpoint path or a state dict, see ``read_lpips_weights``) are loaded into
+    it; nothing is ever downloaded."""
+
+    def __init__(self, weights=None, engine=None, device=None):
+        super().__init__(engine, device)
+        if weights is not None:
+            self._eng.load_lpips(read_lpips_weights(weights))
+
+    def update(self, img1, img2) -> torch.Tensor:
+        return self._add(self._eng.lpips(_t(img1), _t(img2)))
+
+
+def read_lpips_weights(weights):
+    """A state dict for ``Engine.load_lpips`` from a state dict, a local file ``torch.load`` reads, or a list / tuple of those merged in order — the
+    real network comes in two files, torchvision's VGG-16 (``features.N.*``; its ``classifier.*`` tensors are dropped) and the LPIPS ``vgg.pth`` with
+    the ``lin`` layers.  The reference's constructor fetches both (lpips.py:59,69-72); this never does."""
+    if isinstance(weights, (list, tuple)):
+        merged = {}
+        for w in weights:
+            merged.update(read_lpips_weights(w))
+        return merged
+    sd = torch.load(weights, map_location="cpu") if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__") else dict(weights)
+    return {k: v for k, v in sd.items() if not k.startswith("classifier.")}
+
+
+class ReconstructionQuality:
+    """The tokenizer evaluation of tokenizer/tokenizer_image/reconstruction_vq_ddp.py:128-155 for one batch, on the device, plus the LPIPS the tokenizer
+    is trained against (vq_loss.py:93-95).  ``engine`` holds the VQ weights (``__call__``) in the arithmetic to be judged; ``lpips_weights``: a local
+    path, a state dict or a list of them (``read_lpips_weights``), loaded into ``lpips_engine`` (default: ``engine`` itself; pass an fp32 context to judge a
+    bf16 decoder with an exact LPIPS).  ``__call__(images)``, images [B,3,H,W] in [-1,1]: ``vq_encode``, ``vq_decode``, the script's quantiser, PSNR of
+    quantised / 255 against (x + 1) / 2, LPIPS between x and the decoded pixels.  ``compare(pixels_a, pixels_b)`` scores one decoder's pixels against
+    another's the same way.  Both return a dict of fp64 [B] tensors ``psnr`` and ``lpips`` plus the intermediate tensors; nothing leaves the device."""
+
+    def __init__(self, engine: Engine, lpips_weights=None, lpips_engine: Engine = None):
+        self._eng = engine
+        self._lp = lpips_engine if lpips_engine is not None else engine
+        if lpips_weights is not None:
+            self._lp.load_lpips(read_lpips_weights(lpips_weights))
+
+    def _score(self, x: torch.Tensor, pixels: torch.Tensor) -> dict:
+        e = self._eng
+        u8 = e.recon_to_u8(pixels)
+        return {"psnr": e.psnr(u8, x, data_range=1.0, a_map="div255", b_map="half"), "lpips": self._lp.lpips(x, pixels), "pixels": pixels, "u8": u8}
+
+    def __call__(self, images: torch.Tensor) -> dict:
+        e = self._eng
+        x = images.to(device=e.device, dtype=torch.float32).contiguous()
+        B, _, H, W = x.shape
+        down = 2 ** (len(e.cfg.vq.ch_mult) - 1)
+        tokens = e.vq_encode(x)
+        res = self._score(x, e.vq_decode(tokens, H // down, W // down))
+        res["tokens"] = tokens
+        return res
+
+    def compare(self, pixels_a: torch.Tensor, pixels_b: torch.Tensor) -> dict:
+        """``pixels_b`` judged against ``pixels_a`` (both [B,3,H,W] in [-1,1], e.g. the fp32 and the bf16 decoder on the same tokens): PSNR of quantised
+        b / 255 against (a + 1) / 2, LPIPS(a, b).  ``compare(p, p)`` gives LPIPS exactly 0."""
+        e = self._eng
+        a = pixels_a.to(device=e.device, dtype=torch.float32).contiguous()
+        return self._score(a, pixels_b.to(device=e.device, dtype=torch.float32).contiguous())

@@ -470,6 +470,33 @@ def hed_state_dict(seed: int = 11, proj_gain: float = 0.05) -> Dict[str, torch.T
     return sd
 
 
+LPIPS_FEATURES = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))     # the convs of slice1..5 in torchvision's vgg16().features (lpips.py:128-137)
+
+
+def lpips_state_dict(seed: int = 17, spelling: str = "lpips", scaling: bool = True) -> Dict[str, torch.Tensor]:
+    """LPIPS().state_dict() names and shapes (reference tokenizer/tokenizer_image/lpips.py:53-65,99-141): 26 trunk tensors, five 1x1 ``lin`` weights and
+    the two ScalingLayer buffers, 14.7 M parameters.  Trunk: conv weights N(0, 2/fan_in) (He: ``relu5_3`` is neither dead nor saturated after thirteen
+    ReLUs), biases N(0, 0.1^2).  ``lin`` weights are U(0, 0.6): non-negative, as the trained ones are, and a pair of unrelated images lands near the
+    0.1 .. 1 a real LPIPS reports.  ``spelling='torchvision'`` names the trunk ``features.N.*`` as torchvision's vgg16 does (the real LPIPS checkpoint
+    holds only the lin layers); ``scaling=False`` leaves the ScalingLayer buffers out (the loader then takes the constants)."""
+    if spelling not in ("lpips", "torchvision"):
+        raise ValueError(f"spelling {spelling!r}: 'lpips' or 'torchvision'")
+    r = _Rng(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    if scaling:
+        sd["scaling_layer.shift"] = torch.tensor([-.030, -.088, -.188]).view(1, 3, 1, 1)
+        sd["scaling_layer.scale"] = torch.tensor([.458, .448, .450]).view(1, 3, 1, 1)
+    for s, ((ci, co, _), idx) in enumerate(zip(HED_BLOCKS, LPIPS_FEATURES), 1):
+        for i, n in enumerate(idx):
+            cin = ci if i == 0 else co
+            key = f"net.slice{s}.{n}" if spelling == "lpips" else f"features.{n}"
+            sd[key + ".weight"] = r.normal(co, cin, 3, 3, std=(2.0 / (cin * 9)) ** 0.5)
+            sd[key + ".bias"] = r.normal(co, std=0.1)
+    for l, (_, co, _) in enumerate(HED_BLOCKS):
+        sd[f"lin{l}.model.1.weight"] = r.uniform(1, co, 1, 1, lo=0.0, hi=0.6)
+    return sd
+
+
 def dpt_state_dict(cfg: DPTConfig, seed: int = 13) -> Dict[str, torch.Tensor]:
     """DPTForDepthEstimation(cfg).state_dict() names and shapes (transformers modeling_dpt.py, non-hybrid, readout 'project').  The stock initialisation
     (std 0.02, zero biases, zero position embeddings) gives a nearly constant map; here weights are N(0, 1/fan_in) (a ConvTranspose2d whose kernel equals

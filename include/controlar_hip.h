@@ -271,6 +271,44 @@ int car_rmse(car_ctx* ctx, const float* pred, const void* label, int32_t label_d
 int car_pixels_to_u8(car_ctx* ctx, const float* x_nchw, int32_t B, int32_t H, int32_t W, uint8_t* out_hwc, float* float_out, void* stream);
 
 /*
+ * Reconstruction quality — what judges the pixel decoder and the tokenizer's round trip: the LPIPS distance the reference trains its tokenizer
+ * against (tokenizer/tokenizer_image/lpips.py:83-96, vq_loss.py:93-95,124-125) and the PSNR and pixel quantiser of its tokenizer evaluation
+ * (tokenizer/tokenizer_image/reconstruction_vq_ddp.py:128-155).  Deterministic (no atomics), batch-invariant per pair / image, no host synchronisation;
+ * results are fp64.  A refused call leaves the context usable.
+ *
+ * car_lpips — LPIPS.forward in inference (dropout is the identity).  a_nchw, b_nchw: fp32 [B,3,H,W] in [-1,1] (device).  out: fp64 [B], the distance of
+ * pair i; layers_out: fp64 [B,5], the five per-layer terms whose sum in the order 0..4 it is, or NULL.  Per image (x - shift) / scale (a subtraction
+ * and a true division in fp32), the VGG-16 trunk (torchvision features[0:30], taps relu1_2 ... relu5_3) on the kernels of car_hed, per tap and pixel
+ * x / (sqrt(sum_c x_c^2) + 1e-10) for both images, the 1x1 lin of the squared difference, the mean over H x W.  The context's mode sets the trunk's
+ * arithmetic: bf16 operands and stored taps with fp32 accumulation, or fp32 throughout; the head is fp32 per pixel in both, every spatial sum and what
+ * follows fp64.  The head takes the difference of the normalised features directly: identical inputs give exactly 0.0 in every layer, and
+ * car_lpips(a, b) and car_lpips(b, a) are bit-equal.  Both sides at least 16 (four 2x2 pools), H * W at most 2^26.  Weights through car_load_tensor
+ * under "lpips." + key, then car_finalize_weights (which names a missing tensor of a partly loaded family): the trunk as the LPIPS module spells it
+ * (net.slice{1..5}.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias}) or as torchvision does (features.N.{weight,bias}; the LPIPS checkpoint holds
+ * the lin layers only), lin{0..4}.model.1.weight [1,C,1,1], and optionally scaling_layer.shift / .scale [1,3,1,1] (otherwise (-.030, -.088, -.188)
+ * and (.458, .448, .450)).  They travel in the packed cache and may sit next to any other model.
+ */
+int car_lpips(car_ctx* ctx, const float* a_nchw, const float* b_nchw, int32_t B, int32_t H, int32_t W,
+              double* out, double* layers_out, void* stream);
+/*
+ * PSNR per image: out[i] = 10 log10(data_range^2 / mse), mse the fp64 mean of (a - b)^2 over the n elements of image i (skimage's
+ * peak_signal_noise_ratio with an explicit data_range); equal images give +inf.  a, b: [B, n], each fp32 or uint8 (CAR_DT_*), read through its map,
+ * every step rounded to fp32 once: 0 = v, 1 = v / 255 (the script's sample.astype(np.float32) / 255.), 2 = (v + 1) / 2 (its rgb_gt).  Any context.
+ */
+enum { CAR_PSNR_RAW = 0, CAR_PSNR_DIV255 = 1, CAR_PSNR_HALF = 2 };
+int car_psnr(car_ctx* ctx, const void* a, int32_t a_dtype, int32_t a_map, const void* b, int32_t b_dtype, int32_t b_map,
+             int32_t B, int64_t n, double data_range, double* out, void* stream);
+/*
+ * The tokenizer script's quantiser, torch.clamp(127.5 * x + 128.0, 0, 255).to(torch.uint8) (reconstruction_vq_ddp.py:144, val_ddp.py:138): a product
+ * and a sum, each rounded to fp32, a clamp, a truncation — not save_image's rule (car_pixels_to_u8).  x: fp32 [n]; out: uint8 [n], same order.  Any context.
+ */
+int car_recon_to_u8(car_ctx* ctx, const float* x, int64_t n, uint8_t* out, void* stream);
+/* host-only helpers (tests): the name car_load_tensor stores an "lpips." tensor under (0, or -1 for a name outside the network); the pairs one chunk of
+ * car_lpips holds at H x W in a mode (its workspace rule), or -1. */
+int car_debug_lpips_canonical_name(const char* name, char* out, int32_t cap);
+int car_debug_lpips_chunk_pairs(int32_t mode, int32_t H, int32_t W);
+
+/*
  * LineArt control extraction — replaces LineArt.forward (condition/lineart.py:26-86, default constructor: 3 residual blocks, sigmoid; callers
  * sample_t2i.py:110-113,129-132, sample_t2i_MR.py, autoregressive/test/test_t2i.py:177).  img_nchw: fp32 [B,3,H,W] (device), raw 0..255 values as the
  * reference receives them.  out: fp32 [B,1,Ho,Wo] in (0,1) or NULL; control_out: [B,3,Ho,Wo] in the context's element type, = 1 - 2*out replicated over
