@@ -2,7 +2,7 @@
 // packing, finalize, the packed-image cache; engine_attn.hip: the batched multi-head attention every transformer stage calls (attn_bytes / attn_run) and the
 // GPT layer tail shared by the prefill and car_score; engine_encode.hip: resize tables, the control encoder, Canny; engine_generate.hip: prefill, the decode
 // step, generate; engine_score.hip: car_score; engine_t5.hip: the caption encoder; engine_clip.hip: the CLIP score; engine_vq.hip: VQ encode / decode;
-// engine_depth.hip, engine_hed.hip, engine_lineart.hip: the control extractors; engine_lpips.hip: LPIPS, PSNR and the tokenizer script's quantiser; engine_resize.hip, engine_metrics.hip).  Round 4 cut the single 1900-line
+// engine_depth.hip, engine_hed.hip, engine_lineart.hip: the control extractors; engine_lpips.hip: LPIPS, PSNR and the tokenizer script's quantiser; engine_fid.hip: the evaluator's statistics (FID moments, precision / recall, Inception Score); engine_resize.hip, engine_metrics.hip).  Round 4 cut the single 1900-line
 // engine.hip along its stage banners: no behaviour change.  Everything here is internal: the C ABI is include/controlar_hip.h.
 #pragma once
 #include "car_common.h"
@@ -162,6 +162,7 @@ struct car_ctx {
     DevBuf canny_map;    // car_canny: uint8 [B,H,W] candidate/edge map + the "changed" flag
     DevBuf lineart_ws;   // car_lineart: NHWC activations, raw fp32 conv outputs and InstanceNorm partials of one chunk of images (grows on demand)
     DevBuf lpips_ws;     // car_lpips: NHWC activations (two rotating buffers) of both images and the head partials of one chunk of pairs (grows on demand)
+    DevBuf fid_ws;       // car_manifold_radii / car_manifold_pr / car_inception_score: fp16 feature copies, norms, block flags, per-batch lists and status parts, the softmax rows (grows on demand)
     DevBuf hed_ws;       // car_hed: NHWC activations (two rotating buffers) and the side-output partials of one chunk of images (grows on demand)
     car_dpt_config dpt = {}; bool has_dpt = false;   // car_depth_configure
     std::map<int, void*> depth_pos_cache;   // token grid -> T [1 + g*g, hidden]: depth.dpt.embeddings.position_embeddings resized bilinearly

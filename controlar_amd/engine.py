@@ -593,6 +593,93 @@ class Engine:
                     "car_recon_to_u8")
         return out
 
+    # ------------------------------------------------------------------ sample quality (evaluations/c2i/evaluator.py from compute_statistics down)
+    def _acts(self, x: torch.Tensor, what: str) -> torch.Tensor:
+        if x.dim() != 2 or x.shape[0] == 0:
+            raise ValueError(f"{what}: expected non-empty activations [N, D], got {tuple(x.shape)}")
+        return x.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def fid_state(self, D: int) -> torch.Tensor:
+        """An empty moment state for D features (car_fid_state_bytes): fp64 [1 + 2D + D*D] = n | c | sum(x - c) | sum (x - c)(x - c)^T."""
+        nbytes = self.lib.car_fid_state_bytes(int(D))
+        if nbytes <= 0:
+            raise ValueError(f"fid_state: D must be in 1 .. 16384, got {D}")
+        return torch.zeros(nbytes // 8, dtype=torch.float64, device=self.device)
+
+    def fid_accumulate(self, state: torch.Tensor, acts: torch.Tensor) -> torch.Tensor:
+        """Adds acts [n, D] to a moment state in place (car_fid_accumulate): fp64 on the matrix cores, fixed order, the same updates give the same bits."""
+        x = self._acts(acts, "fid_accumulate")
+        n, D = x.shape
+        if state.dtype != torch.float64 or state.numel() != 1 + 2 * D + D * D or not state.is_contiguous() or state.device != x.device:
+            raise ValueError(f"fid_accumulate: the state is not Engine.fid_state({D})")
+        self._check(self.lib.car_fid_accumulate(self._h, C.c_void_p(x.data_ptr()), n, D, C.c_void_p(state.data_ptr()), C.c_void_p(_stream_ptr())),
+                    "car_fid_accumulate")
+        return state
+
+    def fid_finalize(self, state: torch.Tensor, D: int):
+        """(mu fp64 [D], sigma fp64 [D, D]) = np.mean(axis=0), np.cov(rowvar=False) of everything accumulated (car_fid_finalize); at least 2 rows."""
+        if state.dtype != torch.float64 or state.numel() != 1 + 2 * D + D * D:
+            raise ValueError(f"fid_finalize: the state is not Engine.fid_state({D})")
+        mu = torch.empty(D, dtype=torch.float64, device=self.device)
+        sigma = torch.empty(D, D, dtype=torch.float64, device=self.device)
+        self._check(self.lib.car_fid_finalize(self._h, C.c_void_p(state.data_ptr()), D, C.c_void_p(mu.data_ptr()), C.c_void_p(sigma.data_ptr()),
+                                              C.c_void_p(_stream_ptr())), "car_fid_finalize")
+        return mu, sigma
+
+    def manifold_radii(self, feats: torch.Tensor, k: int = 3, row_batch: int = 10000, col_batch: int = 10000) -> torch.Tensor:
+        """ManifoldEstimator.manifold_radii with nhood_sizes = (k,) (car_manifold_radii): fp32 [N], per row the (k+1)-th smallest squared distance to the
+        set, its own included.  fp16 distances with the script's per-block fp32 fallback; the N x N matrix is never written."""
+        x = self._acts(feats, "manifold_radii")
+        N, D = x.shape
+        out = torch.empty(N, dtype=torch.float32, device=self.device)
+        self._check(self.lib.car_manifold_radii(self._h, C.c_void_p(x.data_ptr()), N, D, int(k), int(row_batch), int(col_batch), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(_stream_ptr())), "car_manifold_radii")
+        return out
+
+    def manifold_pr(self, f1: torch.Tensor, r1: torch.Tensor, f2: torch.Tensor, r2: torch.Tensor, row_batch: int = 10000, col_batch: int = 10000):
+        """ManifoldEstimator.evaluate_pr (car_manifold_pr): (status1 uint8 [N1], status2 uint8 [N2], pr fp64 [2]); status1[i] = any_j d_ij <= r2[j],
+        status2[j] = any_i d_ij <= r1[i], pr = (mean status2, mean status1) = (precision, recall) with set 1 the reference batch."""
+        a, b = self._acts(f1, "manifold_pr"), self._acts(f2, "manifold_pr")
+        if a.shape[1] != b.shape[1]:
+            raise ValueError(f"manifold_pr: the sets differ in D: {tuple(a.shape)} and {tuple(b.shape)}")
+        ra, rb = (r.to(device=self.device, dtype=torch.float32).contiguous().reshape(-1) for r in (r1, r2))
+        if ra.numel() != a.shape[0] or rb.numel() != b.shape[0]:
+            raise ValueError(f"manifold_pr: one radius per row, got {ra.numel()} for {a.shape[0]} rows and {rb.numel()} for {b.shape[0]}")
+        s1 = torch.empty(a.shape[0], dtype=torch.uint8, device=self.device)
+        s2 = torch.empty(b.shape[0], dtype=torch.uint8, device=self.device)
+        pr = torch.empty(2, dtype=torch.float64, device=self.device)
+        self._check(self.lib.car_manifold_pr(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(ra.data_ptr()), a.shape[0], C.c_void_p(b.data_ptr()),
+                                             C.c_void_p(rb.data_ptr()), b.shape[0], a.shape[1], int(row_batch), int(col_batch), C.c_void_p(s1.data_ptr()),
+                                             C.c_void_p(s2.data_ptr()), C.c_void_p(pr.data_ptr()), C.c_void_p(_stream_ptr())), "car_manifold_pr")
+        return s1, s2, pr
+
+    def debug_pairwise_distances(self, U: torch.Tensor, V: torch.Tensor):
+        """One block of DistanceBlock.pairwise_distances (car_debug_pairwise_distances, tests): (fp32 [n, m], used_fp32 int32 [1])."""
+        a, b = self._acts(U, "debug_pairwise_distances"), self._acts(V, "debug_pairwise_distances")
+        if a.shape[1] != b.shape[1]:
+            raise ValueError(f"debug_pairwise_distances: the sets differ in D: {tuple(a.shape)} and {tuple(b.shape)}")
+        out = torch.empty(a.shape[0], b.shape[0], dtype=torch.float32, device=self.device)
+        used = torch.empty(1, dtype=torch.int32, device=self.device)
+        self._check(self.lib.car_debug_pairwise_distances(self._h, C.c_void_p(a.data_ptr()), a.shape[0], C.c_void_p(b.data_ptr()), b.shape[0], a.shape[1],
+                                                          C.c_void_p(out.data_ptr()), C.c_void_p(used.data_ptr()), C.c_void_p(_stream_ptr())),
+                    "car_debug_pairwise_distances")
+        return out, used
+
+    def inception_score(self, acts: torch.Tensor, w: torch.Tensor, split_size: int = 5000) -> torch.Tensor:
+        """compute_inception_score (car_inception_score): p = softmax(acts @ w) in fp32, the rest fp64.  acts [N, D], w [D, C] ->
+        fp64 [1 + ceil(N / split_size)]: the score, then every split's value."""
+        x = self._acts(acts, "inception_score")
+        N, D = x.shape
+        if w.dim() != 2 or w.shape[0] != D or w.shape[1] == 0:
+            raise ValueError(f"inception_score: expected a softmax weight [{D}, C], got {tuple(w.shape)}")
+        wm = w.to(device=self.device, dtype=torch.float32).contiguous()
+        if int(split_size) < 1:
+            raise ValueError(f"inception_score: split_size must be positive, got {split_size}")
+        out = torch.empty(1 + -(-N // min(int(split_size), N)), dtype=torch.float64, device=self.device)
+        self._check(self.lib.car_inception_score(self._h, C.c_void_p(x.data_ptr()), N, D, C.c_void_p(wm.data_ptr()), wm.shape[1], int(split_size),
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr())), "car_inception_score")
+        return out
+
     def load_lineart(self, sd: Dict[str, torch.Tensor], finalize: bool = True):
         """LineArt().state_dict() names (condition/lineart.py:26-72: model0.1.weight ... model4.1.bias); the C ABI namespaces them under 'lineart.'."""
         self.load_state_dict({"lineart." + k: v for k, v in sd.items()}, finalize=finalize)

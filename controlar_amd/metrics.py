@@ -256,3 +256,138 @@ class ReconstructionQuality:
         e = self._eng
         a = pixels_a.to(device=e.device, dtype=torch.float32).contiguous()
         return self._score(a, pixels_b.to(device=e.device, dtype=torch.float32).contiguous())
+
+
+# ---------------------------------------------------------------------- sample quality: evaluations/c2i/evaluator.py from compute_statistics down
+def frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """``FIDStatistics(mu1, sigma1).frechet_distance(FIDStatistics(mu2, sigma2), eps)`` (evaluations/c2i/evaluator.py:84-127) on the host, with the same
+    numpy / scipy calls in the same order: ``linalg.sqrtm`` of the product, the retry with ``eps`` on both diagonals where that is not finite, the
+    check of the imaginary part, ``diff.dot(diff) + trace + trace - 2 trace``.  One D^3 matrix square root per evaluation: not a device path."""
+    import warnings
+    try:
+        from scipy import linalg
+    except ImportError as e:
+        raise ImportError("frechet_distance needs scipy (scipy.linalg.sqrtm), which is not installed") from e
+    mu1, mu2 = np.atleast_1d(mu1), np.atleast_1d(mu2)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)
+    if mu1.shape != mu2.shape:
+        raise ValueError(f"the mean vectors differ in length: {mu1.shape}, {mu2.shape}")
+    if sigma1.shape != sigma2.shape:
+        raise ValueError(f"the covariances differ in shape: {sigma1.shape}, {sigma2.shape}")
+    diff = mu1 - mu2
+    covmean, _ = linalg.sqrtm(sigma1.dot(sigma2), disp=False)
+    if not np.isfinite(covmean).all():
+        warnings.warn("fid calculation produces singular product; adding %s to diagonal of cov estimates" % eps)
+        offset = np.eye(sigma1.shape[0]) * eps
+        covmean = linalg.sqrtm((sigma1 + offset).dot(sigma2 + offset))
+    if np.iscomplexobj(covmean):
+        if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+            raise ValueError("Imaginary component {}".format(np.max(np.abs(covmean.imag))))
+        covmean = covmean.real
+    return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
+
+
+class FeatureStatistics:
+    """``Evaluator.compute_statistics`` (evaluator.py:186-189) as a running state on the device: ``update(acts)`` adds a batch [n, D] in fp64 on the matrix
+    cores, ``finalize()`` returns ``(mu, sigma)`` = ``np.mean(axis=0)``, ``np.cov(rowvar=False)`` as fp64 device tensors.  The same updates give the same
+    bits.  (The script's ``mu`` is an fp32 ``np.mean`` of fp32 activations; this one is fp64.)"""
+
+    def __init__(self, engine=None, device=None):
+        self._eng = _engine(engine, device)
+        self._state = None
+        self._D = None
+
+    def update(self, acts) -> None:
+        x = _t(acts)
+        if self._state is None:
+            self._D = int(x.shape[1])
+            self._state = self._eng.fid_state(self._D)
+        elif x.dim() != 2 or x.shape[1] != self._D:
+            raise ValueError(f"update: expected [n, {self._D}], got {tuple(x.shape)}")
+        self._eng.fid_accumulate(self._state, x)
+
+    def finalize(self):
+        if self._state is None:
+            raise ValueError("No activations have been added.")
+        return self._eng.fid_finalize(self._state, self._D)
+
+
+class InceptionScore:
+    """``Evaluator.compute_inception_score`` (evaluator.py:191-204): ``InceptionScore(w)(acts)`` with the softmax weight ``w`` [D, C] of the Inception graph
+    (``_create_softmax_graph``: the last layer without its bias).  ``last_splits`` keeps the per-split values (a device tensor)."""
+
+    def __init__(self, w, split_size=5000, engine=None, device=None):
+        self._eng = _engine(engine, device)
+        self._w = _t(w).to(device=self._eng.device, dtype=torch.float32).contiguous()
+        self.split_size = int(split_size)
+        self.last_splits = None
+
+    def __call__(self, acts) -> float:
+        out = self._eng.inception_score(_t(acts), self._w, self.split_size)
+        self.last_splits = out[1:]
+        return float(out[0])
+
+
+class PrecisionRecall:
+    """``Evaluator.compute_prec_recall`` (evaluator.py:206-214) with the ``ManifoldEstimator`` defaults: ``PrecisionRecall()(ref_acts, sample_acts)`` ->
+    ``(precision, recall)``.  ``radii`` and ``status`` of the last call stay available as device tensors."""
+
+    def __init__(self, k=3, row_batch=10000, col_batch=10000, engine=None, device=None):
+        self._eng = _engine(engine, device)
+        self.k, self.row_batch, self.col_batch = int(k), int(row_batch), int(col_batch)
+        self.radii = self.status = None
+
+    def __call__(self, ref_acts, sample_acts):
+        e = self._eng
+        a, b = _t(ref_acts).to(e.device), _t(sample_acts).to(e.device)
+        r1 = e.manifold_radii(a, self.k, self.row_batch, self.col_batch)
+        r2 = e.manifold_radii(b, self.k, self.row_batch, self.col_batch)
+        s1, s2, pr = e.manifold_pr(a, r1, b, r2, self.row_batch, self.col_batch)
+        self.radii, self.status = (r1, r2), (s1, s2)
+        p = pr.cpu()
+        return float(p[0]), float(p[1])
+
+
+class SampleQuality:
+    """The five numbers of evaluations/c2i/evaluator.py's ``main`` from activations that are already on the device (the Inception tower that produces them
+    is not part of this package).  The reference side is either activations (``ref_acts`` [N, D], and ``ref_acts_spatial`` for sFID) or the precomputed
+    moments the published reference batches carry (``ref_stats=(mu, sigma)``, ``ref_stats_spatial=(mu_s, sigma_s)``); precision and recall need
+    ``ref_acts``.  ``__call__(sample_acts, sample_acts_spatial=None, softmax_weight=None)`` returns a dict with ``inception_score``, ``fid``, ``sfid``,
+    ``precision`` and ``recall`` (``None`` for what its inputs were not given).  Activations never leave the device; the two moment pairs go to the
+    host for ``frechet_distance``."""
+
+    def __init__(self, ref_acts=None, ref_stats=None, ref_acts_spatial=None, ref_stats_spatial=None, softmax_weight=None, split_size=5000, k=3,
+                 row_batch=10000, col_batch=10000, batch=10000, engine=None, device=None):
+        self._eng = _engine(engine, device)
+        self._batch = int(batch)
+        self._ref_acts = None if ref_acts is None else _t(ref_acts).to(self._eng.device)
+        self._w, self._split = softmax_weight, split_size
+        self._pr = PrecisionRecall(k, row_batch, col_batch, engine=self._eng)
+        self._ref = self._host(ref_stats) if ref_stats is not None else (self._moments(self._ref_acts) if self._ref_acts is not None else None)
+        self._ref_s = (self._host(ref_stats_spatial) if ref_stats_spatial is not None
+                       else (self._moments(_t(ref_acts_spatial)) if ref_acts_spatial is not None else None))
+
+    @staticmethod
+    def _host(stats):
+        mu, sigma = stats
+        return tuple(np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v) for v in (mu, sigma))
+
+    def _moments(self, acts):
+        fs = FeatureStatistics(engine=self._eng)
+        for i in range(0, acts.shape[0], self._batch):
+            fs.update(acts[i:i + self._batch])
+        return self._host(fs.finalize())
+
+    def __call__(self, sample_acts, sample_acts_spatial=None, softmax_weight=None) -> dict:
+        x = _t(sample_acts).to(self._eng.device)
+        w = softmax_weight if softmax_weight is not None else self._w
+        res = {"inception_score": None, "fid": None, "sfid": None, "precision": None, "recall": None}
+        if w is not None:
+            res["inception_score"] = InceptionScore(w, self._split, engine=self._eng)(x)
+        if self._ref is not None:
+            res["fid"] = float(frechet_distance(*self._moments(x), *self._ref))
+        if self._ref_s is not None and sample_acts_spatial is not None:
+            res["sfid"] = float(frechet_distance(*self._moments(_t(sample_acts_spatial)), *self._ref_s))
+        if self._ref_acts is not None:
+            res["precision"], res["recall"] = self._pr(self._ref_acts, x)
+        return res

@@ -309,6 +309,47 @@ int car_debug_lpips_canonical_name(const char* name, char* out, int32_t cap);
 int car_debug_lpips_chunk_pairs(int32_t mode, int32_t H, int32_t W);
 
 /*
+ * Sample quality — the statistics half of evaluations/c2i/evaluator.py (everything from compute_statistics down): the moments behind FID and sFID,
+ * improved precision / recall, the Inception Score.  Inputs are activations [N, D] already on the device; the Inception tower that produces them
+ * is not part of the library, and the Fréchet distance itself (one D^3 matrix square root per evaluation) is host code
+ * (controlar_amd.metrics.frechet_distance).  No weights, any context; the context's mode changes no bit.  Deterministic: fixed summation orders, no
+ * floating-point atomics.  A refused call leaves the context usable.
+ *
+ * Moments (compute_statistics, :186-189) as a running fp64 state the caller owns: car_fid_state_bytes(D) bytes of device memory (0 for a D outside
+ * 1..16384), all zero = empty; fp64 [1 + 2D + D*D] = n | c [D] | sum(x - c) [D] | sum (x - c)(x - c)^T [D][D].  c is fixed by the first update as
+ * that batch's column mean rounded to fp32; products accumulate on v_mfma_f64_16x16x4_f64 as one k-ordered chain over all updates.
+ * car_fid_accumulate adds acts fp32 [n, D] (n >= 1).  car_fid_finalize writes mu fp64 [D] = np.mean(axis=0) and sigma fp64 [D, D] =
+ * np.cov(rowvar=False) (ddof 1; exactly symmetric, written in full); it reads n back, so it waits for the stream, and refuses a state of fewer
+ * than 2 rows.
+ */
+int64_t car_fid_state_bytes(int32_t D);
+int car_fid_accumulate(car_ctx* ctx, const float* acts, int64_t n, int32_t D, void* state, void* stream);
+int car_fid_finalize(car_ctx* ctx, const void* state, int32_t D, double* mu, double* sigma, void* stream);
+/*
+ * Precision and recall (ManifoldEstimator.manifold_radii / evaluate_pr over DistanceBlock, :260-293, :337-442, nhood_sizes = (k,), no percentile
+ * clamp).  Squared distances are computed per (row batch x column batch) block in fp16 and, where a block's fp16 result is not all finite, again in
+ * fp32 for that whole block (a device flag per block; no host round trip).  The fp16 arithmetic, which TensorFlow leaves to its backend, is defined
+ * as: features rounded to fp16 (nearest even), D padded with zeros to a multiple of 32; nu, nv = fl16 of the fp32 sum of the fp16-rounded squares;
+ * mm = fl16 of the v_mfma_f32_16x16x32_f16 product (exact products, fp32 accumulation); d = max(fl16(fl16(nu - fl16(2 mm)) + nv), 0), widened to
+ * fp32.  The fp32 block: the same expression with one fp32 rounding per operation on v_mfma_f32_16x16x4_f32.  Nothing of size N x N is written.
+ * car_manifold_radii: radii[i] = the (k+1)-th smallest of row i's N distances, its own included (0 <= k <= 7, k + 1 <= N).
+ * car_manifold_pr: status1[i] = any_j d_ij <= r2[j], status2[j] = any_i d_ij <= r1[i] (uint8 0 / 1; d over rows of f1 and rows of f2),
+ * pr = (mean status2, mean status1) = (precision, recall) when set 1 is the reference batch, as compute_prec_recall passes it.
+ * row_batch, col_batch: the script's 10000 / 10000; they decide which distances share a fallback and nothing else.
+ * car_debug_pairwise_distances (tests): one block's distances, out fp32 [n, m], and *used_fp32 (device int32) = 1 if the block fell back.
+ */
+int car_manifold_radii(car_ctx* ctx, const float* feats, int64_t N, int32_t D, int32_t k, int64_t row_batch, int64_t col_batch, float* radii, void* stream);
+int car_manifold_pr(car_ctx* ctx, const float* f1, const float* r1, int64_t N1, const float* f2, const float* r2, int64_t N2, int32_t D,
+                    int64_t row_batch, int64_t col_batch, uint8_t* status1, uint8_t* status2, double* pr, void* stream);
+int car_debug_pairwise_distances(car_ctx* ctx, const float* U, int64_t n, const float* V, int64_t m, int32_t D, float* out, int32_t* used_fp32, void* stream);
+/*
+ * Inception Score (compute_inception_score, :191-204): p = softmax(acts . w) in fp32 (w fp32 [D, C], no bias: _create_softmax_graph), everything
+ * behind p in fp64; per split of split_size rows exp(mean_rows sum_c p (log p - log mean_rows p)).  out fp64 [1 + ceil(N / split_size)]: the mean of
+ * the splits, then every split.  A probability of exactly 0 gives NaN, as in the script.
+ */
+int car_inception_score(car_ctx* ctx, const float* acts, int64_t N, int32_t D, const float* w, int32_t C, int64_t split_size, double* out, void* stream);
+
+/*
  * LineArt control extraction — replaces LineArt.forward (condition/lineart.py:26-86, default constructor: 3 residual blocks, sigmoid; callers
  * sample_t2i.py:110-113,129-132, sample_t2i_MR.py, autoregressive/test/test_t2i.py:177).  img_nchw: fp32 [B,3,H,W] (device), raw 0..255 values as the
  * reference receives them.  out: fp32 [B,1,Ho,Wo] in (0,1) or NULL; control_out: [B,3,Ho,Wo] in the context's element type, = 1 - 2*out replicated over
