@@ -13,7 +13,9 @@
 //   Softmax statistics are per query = per lane column: reductions are two xor-shuffles (16, 32) across the four lane groups.
 //
 // Rounding points (fast mode): scores stay fp32 (as the fused SDPA kernels the reference runs), probabilities are rounded to bf16
-// before P·V, the output is rounded once.  T5 mode reproduces the eager op sequence rnd(rnd(q·k) + bias).
+// before P·V, the output is rounded once.  T5 mode reproduces the eager op sequence rnd(rnd(q·k) + bias); a sequence whose keys are ALL masked gives the
+// uniform distribution over its Tk keys (the mean of the V rows), as the additive finfo.min mask and t5_softmax_kernel do.  Causal mode cannot meet that case:
+// the diagonal always attends.  experiments/attn_check.hip pins all three modes to exact and fp64 references.
 #include "car_common.h"
 #include "kernel_params.h"
 
@@ -31,6 +33,14 @@ __global__ __launch_bounds__(256) void flash64_kernel(FlashP p) {
     const bf16_t* kp = p.k + b * p.k_sb + h * 64;
     const bf16_t* vp = p.vt + b * p.vt_sb + (long)h * 64 * p.vt_ld;
     const unsigned char* mk = MODE ? p.mask + b * p.Tk : nullptr;
+    // T5 mode, every key of the sequence masked: the additive finfo.min form absorbs score and bias alike, so all Tk keys tie — the uniform distribution
+    // t5_softmax_kernel (t5.hip) gives.  Uniform in the workgroup (one b); any other mask takes the statements below unchanged.
+    bool none = false;
+    if (MODE == 2) {
+        int any = 0;
+        for (int j = tid; j < p.Tk; j += 256) any |= mk[j] != 0;
+        none = !__syncthreads_or(any);
+    }
 
     bf16x8 qf[QT][2];
     int qi[QT];
@@ -115,12 +125,12 @@ __global__ __launch_bounds__(256) void flash64_kernel(FlashP p) {
                 for (int r = 0; r < 4; ++r) {
                     const int j = j0 + r;
                     float x = s[kt][t][r] * p.scale;
-                    if (MODE == 2) x = bf2f(f2bf(bf2f(f2bf(x)) + bz[r]));
+                    if (MODE == 2) x = none ? 0.f : bf2f(f2bf(bf2f(f2bf(x)) + bz[r]));
                     const int inr = j < p.Tk;
                     int ok;
                     if (MODE == 0) ok = inr;
                     else if (MODE == 1) ok = inr & (j <= qi[t]) & ((((mkb[kt] >> (8 * r)) & 1u) != 0) | (j == qi[t]));
-                    else ok = inr & (((mkb[kt] >> (8 * r)) & 1u) != 0);
+                    else ok = inr & ((((mkb[kt] >> (8 * r)) & 1u) != 0) | none);
                     x = ok ? x : -INFINITY;
                     v[kt][r] = x; mx = fmaxf(mx, x);
                 }

@@ -20,7 +20,8 @@ extern "C" void car_launch_t5_prep(const long long* ids, const long long* mask, 
 }
 
 // rows ordered (b, head, i).  bias: T-rounded values as fp32 [heads][Tq][ncols].  A row whose keys are all masked degenerates to the
-// uniform distribution exactly as the additive finfo.min form does.
+// uniform distribution over all ncols keys exactly as the additive finfo.min form does (oracle/t5_oracle.py); flash64_kernel<_, 2> (attn.hip) does the same,
+// and experiments/attn_check.hip holds both to the mean of the V rows bit for bit.
 template <typename T>
 __global__ __launch_bounds__(128) void t5_softmax_kernel(const float* S, long lds, void* P_, long ldp, int ncols, const float* bias,
                                                          const unsigned char* mask, int Tq, int n_head) {

@@ -75,6 +75,25 @@ def test_generic_gemm_and_conv_kernels_against_exact_integer_references():
     assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
 
 
+def test_batched_attention_against_exact_and_fp64_references():
+    """attn_run (engine_attn.hip) driven by experiments/attn_check.hip (quick mode, built with -DCAR_DEV_KNOBS so that CAR_NO_FLASH is live; that switch is read once
+    per process, hence two invocations): flash64_kernel<QT, MODE> in the bf16 mode, transpose_pad -> car_launch_gemm -> softmax_wave / softmax_reg / softmax /
+    t5_softmax kernel -> car_launch_gemm in the exact mode (first run) and in the bf16 mode (second run).  H = 2, nb = 3, T in {1, 15, 16, 17, 31, 32, 33, 63, 64, 65,
+    120, 128, 129, 192, 193, 197, 257}, all three mask kinds at every T, both input layouts (ld = D, ld = 3D), 40 x 70 straight through car_launch_flash64; every case
+    on a poisoned arena of which everything but out and the scratch planes is compared with memcmp, V^T and P pad columns zero, two runs with equal bits.  No
+    tolerance: Q = 0 with integer V (every row one of the three candidate 1 / count: pins the attended set under left / right padding, holes, a fully masked
+    sequence — T5: uniform over all keys in both forms — and a 0 / -128 bias per head and query), one-hot scores whose keys are >= 128 apart (the output is the bits
+    of the winner's V row, winners at 0 / 15 / 16 / 31 / 32 / 33 / T - 1, losers +-3e38), softmax_reg_kernel == softmax_kernel, window invariance of the wave and
+    register softmax for c in {16, 48}, every refusal of car_launch_flash64 and its way through attn_run.  Dense integer Q, K and bf16 V, bias against an fp64 softmax on
+    every element under the bound derived in the harness header from the rounding points of each form (the exact mode's at fp32 level)."""
+    exe = _build("attn_check", extra=("-DCAR_DEV_KNOBS",))
+    for env in ({}, {"CAR_NO_FLASH": "1"}):
+        out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600, env={**os.environ, **env})
+        assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
+        assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
+        assert ("CAR_NO_FLASH" in out.stdout) == bool(env)
+
+
 def test_bf16_decode_kernels_against_exact_integer_references():
     """decode2.hip (experiments/decode_check.hip, quick mode): dec_gemm_kernel, rmsnorm2_kernel and the two writers of the packed KV cache (the EPI_QKV epilogue,
     prefill_rope_kv2_kernel) through the real launchers, every dec_gemm case asserting its car_dec_gemm_route value (I, J, WAVES, F8, NORM) first.  Operands are

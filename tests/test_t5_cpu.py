@@ -63,6 +63,30 @@ def test_padded_keys_do_not_influence_valid_rows():
     assert torch.equal(a[v], b[v])
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_all_masked_sequence_attends_uniformly_over_all_keys(dtype):
+    """The additive finfo.min mask absorbs score and position bias alike when EVERY key of a sequence is masked: all keys tie and the softmax is the uniform
+    distribution over all T keys, i.e. the context is the mean of the V rows.  t5_softmax_kernel and flash64_kernel<_, 2> are pinned to this on the GPU
+    (experiments/attn_check.hip, tests/test_kernels_gpu.py); this is the oracle's side of the same input."""
+    cfg = C.tiny_t5()
+    sd = {k: v.to(dtype) for k, v in synth.t5_state_dict(cfg).items() if torch.is_floating_point(v)}
+    T, H, dk = 9, cfg.num_heads, cfg.d_kv
+    torch.manual_seed(3)
+    x = torch.randn(2, T, cfg.d_model).to(dtype)
+    mask = torch.ones(2, T, dtype=torch.long)
+    mask[0] = 0                                        # sequence 0: every key masked; sequence 1: none
+    ext = (1.0 - mask[:, None, None, :].to(dtype)) * torch.finfo(dtype).min
+    pb = TO.position_bias(sd["encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"], T,
+                          cfg.relative_attention_num_buckets, cfg.relative_attention_max_distance)
+    pfx = "encoder.block.0.layer.0.SelfAttention."
+    got = TO.self_attention(x, sd, pfx, H, dk, pb + ext)[0]
+    v = (x[0] @ sd[pfx + "v.weight"].t()).view(T, H, dk)
+    p = torch.full((H, T, T), 1.0 / T).to(dtype)      # the uniform distribution, cast as the oracle casts its probabilities
+    ctx = torch.matmul(p, v.transpose(0, 1)).transpose(0, 1).reshape(T, H * dk)
+    want = ctx @ sd[pfx + "o.weight"].t()
+    assert torch.equal(got, want)
+
+
 def test_t5_config_from_hf_rejects_relu():
     from controlar_amd.t5 import t5_config_from_hf
     d = dict(vocab_size=32128, d_model=2048, d_kv=64, num_heads=32, d_ff=5120, num_layers=24, feed_forward_proj="gated-gelu")
