@@ -162,6 +162,7 @@ SYMBOLS = {
     "car_debug_f32_to_e4m3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "car_debug_split_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "car_debug_attn_edge_mask": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "car_debug_prompt_window": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "car_debug_control_tokens": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
 }
 

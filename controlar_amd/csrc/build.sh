@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
-SRCS="gemm gemm_split ops decode decode2 decode_f32 pack canny resample lineart hed dpt t5 attn engine engine_weights engine_attn engine_encode engine_generate engine_t5 engine_vq engine_lineart engine_hed engine_depth engine_resize metrics engine_metrics score engine_score clip engine_clip lpips engine_lpips fid engine_fid"
+SRCS="gemm gemm_split ops decode decode2 decode_f32 pack canny resample lineart hed dpt t5 attn engine engine_weights engine_attn engine_prompt engine_encode engine_generate engine_t5 engine_vq engine_lineart engine_hed engine_depth engine_resize metrics engine_metrics score engine_score clip engine_clip lpips engine_lpips fid engine_fid"
 mkdir -p _obj _obj_dev
 # build id = hash of every source: the packed-weight cache (car_export_packed / car_import_packed) is private to one build
 BID=$( (cat *.hip *.h ../../include/controlar_hip.h; echo "$FLAGS"; $HIPCC --version 2>/dev/null) | sha1sum | cut -c1-40)

@@ -1,5 +1,5 @@
-// engine_attn.hip — the batched multi-head attention of the host side (attn_bytes / attn_run) and the second half of a GPT layer (gpt_layer_tail):
-// what car_encode_control, car_depth, both CLIP towers, car_t5_encode, the prefill of car_generate and car_score share.
+// engine_attn.hip — the batched multi-head attention of the host side (attn_bytes / attn_run): what car_encode_control, car_depth, both CLIP towers,
+// car_t5_encode and the prompt pass of car_generate and car_score (engine_prompt.hip) share.
 // (one of the translation units behind include/controlar_hip.h; shared declarations: engine_internal.h)
 #include "engine_internal.h"
 
@@ -13,7 +13,7 @@ AttnBytes attn_bytes(const car_ctx* c, int nb, int T, int H, int hd) {
     return b;
 }
 
-// V^T into ws[6], then flash64 (use_flash), else S = scale * Q K^T (fp32, ws[4]) -> the softmax of the mask kind (P, ws[5]) -> out = P V.
+// V^T into ws[WS_ATTN_VT], then flash64 (use_flash), else S = scale * Q K^T (fp32, ws[WS_ATTN_S]) -> the softmax of the mask kind (P, ws[WS_ATTN_P]) -> out = P V.
 // Non-zero: the fused kernel was chosen and car_launch_flash64 refused the shape; nothing further was launched (S and P were never sized: there is no
 // falling back).  No caller can see that: flash64 (attn.hip, car_launch_flash64) wants token and sequence strides in multiples of 8 elements, 16-byte
 // aligned q, k and V^T, 8-byte aligned out, vt_ld a multiple of 32 that covers Tk, and Tq == Tk under the causal mask.  use_flash means hd == 64, so every
@@ -21,7 +21,7 @@ AttnBytes attn_bytes(const car_ctx* c, int nb, int T, int H, int hd) {
 // of rows * width elements or, in the packed layout, one width; vt_ld = rup(T, 32); Tq = Tk = T.
 int attn_run(car_ctx* c, const AttnCall& a, hipStream_t st) {
     const int mode = c->mode, T = a.T, H = a.H, hd = a.hd, nb = a.nb, D = H * hd, Tpad = (int)rup(T, 32);
-    float* S = (float*)c->ws[4].p; void* P = c->ws[5].p; void* vT = c->ws[6].p;
+    float* S = (float*)c->ws[WS_ATTN_S].p; void* P = c->ws[WS_ATTN_P].p; void* vT = c->ws[WS_ATTN_VT].p;
     car_launch_transpose_pad(mode, a.v, a.ld, (long)T * a.ld, vT, nb, T, Tpad, D, st);
     if (use_flash(c, hd)) {
         FlashP f; memset(&f, 0, sizeof(f));
@@ -47,20 +47,4 @@ int attn_run(car_ctx* c, const AttnCall& a, hipStream_t st) {
         car_launch_gemm(mode, AMODE_PLAIN, &q, st);
     }
     return 0;
-}
-
-// h += wo(att); xn = ffn_norm(h); h += w2(silu(w1 xn) * w3 xn) over `rows` rows of layer prefix L (gpt_t2i.py:291-295).  mid holds rows * ffn_hidden
-// elements, in the fp32 mode three times that: the interleaved w13 output sits behind the gated product.
-void gpt_layer_tail(car_ctx* c, const std::string& L, void* h, void* xn, const void* att, void* mid, long rows, hipStream_t st) {
-    const car_config& g = c->cfg; const int mode = c->mode, D = g.dim, Fh = g.ffn_hidden;
-    { GemmP q = gp(att, D, Wp(c, L + "attention.wo.weight"), D, h, D, (int)rows, D, D); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
-    { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, L + "ffn_norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rows, st); }
-    if (mode == CAR_BF16) {
-        GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid, Fh, (int)rows, 2 * Fh, D); q.swiglu = 1; car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-    } else {
-        void* mid2 = off(mid, (size_t)rows * Fh, c->esz);
-        GemmP q = gp(xn, D, Wp(c, L + "feed_forward.w13.weight"), D, mid2, 2 * Fh, (int)rows, 2 * Fh, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st);
-        car_launch_swiglu(mode, mid2, mid, rows, Fh, st);
-    }
-    { GemmP q = gp(mid, Fh, Wp(c, L + "feed_forward.w2.weight"), Fh, h, D, (int)rows, D, Fh); q.R = h; q.ldr = D; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
 }

@@ -91,7 +91,7 @@ static int clip_ready(car_ctx* c, const char* who) {
 }
 
 // The pre-norm layers of one tower over `nb` sequences of Tn rows in h (modeling_clip.py CLIPEncoderLayer): h += out_proj(attn(LN1 h)); h += fc2(quick_gelu(fc1(LN2 h))).
-// causal: the text tower's mask (key j <= query i, no padding mask).  Scratch: ws[2] xn, ws[3] q|k|v, ws[4] S, ws[5] P, ws[6] V^T, ws[7] mid, ws[8] ctx.
+// causal: the text tower's mask (key j <= query i, no padding mask).  Scratch: ws[2] xn, ws[3] q|k|v, ws[WS_ATTN_S], ws[WS_ATTN_P], ws[WS_ATTN_VT], ws[7] mid, ws[8] ctx.
 static int clip_layers(car_ctx* c, const std::string& tower, int layers, void* h, int nb, int Tn, int D, int nh, int F, bool causal, hipStream_t st) {
     const int mode = c->mode; const size_t e = c->esz; const float eps = c->clip.ln_eps;
     const long rows = (long)nb * Tn;
@@ -124,9 +124,9 @@ static int clip_scratch(car_ctx* c, int CH, int Tn, int D, int nh, int F, size_t
     NEED(c, c->ws[1], (size_t)rows * D * e);
     NEED(c, c->ws[2], (size_t)rows * D * e);
     NEED(c, c->ws[3], (size_t)rows * 3 * D * e);
-    if (ab.S) NEED(c, c->ws[4], ab.S);
-    if (ab.P) NEED(c, c->ws[5], ab.P);
-    NEED(c, c->ws[6], ab.Vt);
+    if (ab.S) NEED(c, c->ws[WS_ATTN_S], ab.S);
+    if (ab.P) NEED(c, c->ws[WS_ATTN_P], ab.P);
+    NEED(c, c->ws[WS_ATTN_VT], ab.Vt);
     NEED(c, c->ws[7], (size_t)rows * F * e);
     NEED(c, c->ws[8], (size_t)rows * D * e);
     return 0;
@@ -225,7 +225,7 @@ extern "C" int car_clip_encode_text(car_ctx* c, const int64_t* ids, int32_t B, i
     const int D = k.text_width, nh = k.text_heads, F = k.text_mlp;
     const int mode = c->mode; const size_t e = c->esz;
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
-    if (!c->host_flags) { HIPCHK(c, hipHostMalloc((void**)&c->host_flags, 64, hipHostMallocMapped)); memset(c->host_flags, 0, 64); }
+    if (ensure_host_flags(c)) return -1;
     const int CH = clip_chunk(c, B, T, nh);
     if (clip_scratch(c, CH, T, D, nh, F, (size_t)2 * CH * D)) return -1;
     NEED(c, c->clip_ones, (size_t)CH * T);

@@ -213,9 +213,9 @@ extern "C" int car_depth(car_ctx* c, const float* pixel_values, int32_t B, int32
     NEED(c, c->ws[2], (size_t)CH * Tn * D * e);            // y (normed) / tok
     NEED(c, c->ws[3], (size_t)CH * Tn * 3 * D * e);        // q | k | v (separate planes)
     const AttnBytes ab = attn_bytes(c, CH, Tn, nh, hd);
-    if (ab.S) NEED(c, c->ws[4], ab.S);                     // S fp32
-    if (ab.P) NEED(c, c->ws[5], ab.P);                     // P
-    NEED(c, c->ws[6], ab.Vt);                              // V^T
+    if (ab.S) NEED(c, c->ws[WS_ATTN_S], ab.S);                     // S fp32
+    if (ab.P) NEED(c, c->ws[WS_ATTN_P], ab.P);                     // P
+    NEED(c, c->ws[WS_ATTN_VT], ab.Vt);                              // V^T
     NEED(c, c->ws[7], (size_t)CH * Tn * d.mlp * e);        // mlp mid
     NEED(c, c->ws[8], (size_t)CH * Tn * D * e);            // ctx
     // development build only: time the backbone alone (outputs are not written), and the reference's order up-sample -> 1x1 projection (DPT section)

@@ -1,4 +1,4 @@
-// engine_generate.hip — stages D-G: text prefix, control tokens, prefill, the captured decode step (bf16 fast path and the exact fp32 path), car_generate / car_generate_c2i
+// engine_generate.hip — stages D-G: the prefill (the prompt pass of engine_prompt.hip on car_generate's row layout), the captured decode step (bf16 fast path and the exact fp32 path), car_generate / car_generate_c2i
 // (one of the translation units behind include/controlar_hip.h; shared declarations: engine_internal.h)
 #include "engine_internal.h"
 
@@ -411,7 +411,7 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     if (rows && use_cfg && !c2i && use_control) for (int i = 0; i < B; ++i) row_strength |= rows[i].control_strength != 1.0f;
     const int S_max = (int)rup(T + n_new, 8);                       // gpt_t2i.py:395
     const int SA = c->mode == CAR_BF16 ? (int)rup(S_max, 32) : S_max;   // fast mode: packed KV streams hold whole 32-position blocks (decode2.hip)
-    const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok, li = g.n_layer / 3;
+    const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok;
     const int mode = c->mode; const size_t e = c->esz;
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
 
@@ -438,25 +438,25 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     const size_t kv_e = (fast && g.kv_cache_fp8) ? 1 : e;        // opt-in e4m3 KV cache: one byte per element
     NEED(c, c->kv, (size_t)g.n_layer * 2 * kv_layer * kv_e);
     const bool kv_fresh = c->kv.cap != kv_cap_before;
-    const long rowsP = (long)b * T;
-    NEED(c, c->ws[0], (size_t)b * T * g.caption_dim * e);                     // text input (cond | uncond)
-    NEED(c, c->ws[1], (size_t)rowsP * D * e);                                 // h (prefill)
-    NEED(c, c->ws[2], (size_t)rowsP * D * e);                                 // xn
-    NEED(c, c->ws[3], (size_t)rowsP * 3 * D * e);                             // qkv
+    const long rowsP = (long)b * T;                                           // sizes the buffers; the prefill computes b * Tv rows, Tv <= T (the window below)
+    NEED(c, c->ws[WS_TEXT], (size_t)b * T * g.caption_dim * e);               // text input (cond | uncond)
+    NEED(c, c->ws[WS_H], (size_t)rowsP * D * e);                              // h (prefill)
+    NEED(c, c->ws[WS_XN], (size_t)rowsP * D * e);
+    NEED(c, c->ws[WS_QKV], (size_t)rowsP * 3 * D * e);
     const AttnBytes ab = attn_bytes(c, b, T, Hn, 64);                         // fused prefill attention: no score / probability tensors
-    if (ab.S) NEED(c, c->ws[4], ab.S);                                        // S
-    if (ab.P) NEED(c, c->ws[5], ab.P);                                        // P
-    NEED(c, c->ws[6], ab.Vt);                                                 // V^T
-    NEED(c, c->ws[7], (size_t)rowsP * (mode == CAR_BF16 ? Fh : 3 * Fh) * e);  // ffn mid (+ interleaved w13 out in exact mode)
-    NEED(c, c->ws[8], (size_t)rowsP * D * e);                                 // attention out
-    NEED(c, c->ws[9], (size_t)b * V * 4);                                     // logits fp32
+    if (ab.S) NEED(c, c->ws[WS_ATTN_S], ab.S);
+    if (ab.P) NEED(c, c->ws[WS_ATTN_P], ab.P);
+    NEED(c, c->ws[WS_ATTN_VT], ab.Vt);
+    NEED(c, c->ws[WS_MID], (size_t)rowsP * (mode == CAR_BF16 ? Fh : 3 * Fh) * e);  // ffn mid (+ interleaved w13 out in exact mode)
+    NEED(c, c->ws[WS_ATT_OUT], (size_t)rowsP * D * e);
+    NEED(c, c->ws[WS_LOGITS], (size_t)b * V * 4);                             // fp32
     // exact mode: KV splits with boundaries fixed in ABSOLUTE positions (AF_SPLIT rows each), whatever the batch — the split layout fixes the order in
     // which a row's softmax partial sums are folded, so a sequence decodes to the same bits in a batch of 1 and in a batch of 384 (every other
     // exact-mode kernel sums one fixed-order fp32 chain per output): tests/test_parity_gpu.py::test_exact_mode_is_batch_invariant,
     // bench.py --precision fp32 (row 0 = the XL golden).
     const int nsplit = fast ? attn_splits(b * Hn) : pl.ch[0].nsplit;
-    NEED(c, c->ws[10], (size_t)b * Hn * nsplit * 66 * 4);                     // split-KV partials
-    NEED(c, c->ws[11], (size_t)B * (use_control ? n_tok : 1) * D * e);        // condition_mlp output / mlp mid
+    NEED(c, c->ws[WS_PARTS], (size_t)b * Hn * nsplit * 66 * 4);               // split-KV partials
+    NEED(c, c->ws[WS_CTRL_MLP], (size_t)B * (use_control ? n_tok : 1) * D * e);   // condition_mlp output
     // device scalars: [16 ints: (pos, step) of up to 8 chains] [cur_tok: b ints] [jmin: b ints] [jmin_min: 4 ints] [SampleDyn, 16-byte aligned]
     NEED(c, c->scal, (size_t)(16 + 2 * b + 4) * 4 + 16 + sizeof(SampleDyn) + 16);
     NEED(c, c->rowimg, (size_t)b * 4);
@@ -484,109 +484,47 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
     if (rows && rows_upload(c, rows, B, st)) return -1;
     const SampleRow* rows_dev = rows ? (const SampleRow*)c->rows_dev.p : nullptr;
     if (emb_mask) car_launch_mask_first_valid((const unsigned char*)c->maskb.p, jmin, b, T, st);
-    // ---- prefill window (round 4; SURVEY Appendix E: result-preserving).  Prompts are LEFT-padded (sample_t2i.py:146-160): a pad column is masked for every
-    // row of the prefill and for every decode step, so the hidden states and K / V of pad rows influence nothing that is returned — yet the reference (and
-    // rounds 1-3 here) pushed all T = 120 rows of every sequence through the 36 layers.  The prefill now runs on the LAST Tv rows only, Tv = the longest valid
-    // prompt of the batch rounded up to 8 (8-40 of 120 in the reference's caption statistics): every kernel of the prefill sees sequences of Tv rows, cache rows
-    // and rope rows are offset by t0 = T - Tv, the mask by the same columns.  A valid row's arithmetic is unchanged (masked keys contributed exact zeros), so
-    // exact-mode tokens stay bit-identical.  Cost: the window size has to be known on the HOST before the prefill is enqueued — from the caller's
-    // car_sampling.first_valid_hint (no wait at all), else by ONE 4-byte device-to-host read of the batch minimum of `jmin`, the only host wait of car_generate
-    // and only when a mask is given (development build: CAR_NO_PREFILL_WINDOW=1 keeps all T rows and no wait).
+    // ---- prefill window (engine_prompt.hip): the prefill runs on the valid tail [t0, T) of the left-padded prompts, t0 a multiple of 16.  Its only host wait is
+    // the 4-byte read of a call that brings a mask and no first_valid_hint (development build: CAR_NO_PREFILL_WINDOW=1 keeps all T rows and no wait).
     int Tv = T, t0 = 0;
-    if (emb_mask && !c2i && T > 8 && T % 8 == 0 && (mode == CAR_BF16 || T <= 128) && !CAR_KNOB("CAR_NO_PREFILL_WINDOW")) {
-        int hmin = 0;
-        const bool hinted = sp->first_valid_hint > 0;
-        if (hinted) {
-            // the caller knows a lower bound of the first valid prompt position (it built the mask on the host): nothing is read back, the call only enqueues
-            // (the device checks the bound below and raises a sticky flag if valid rows would fall outside the window)
-            hmin = sp->first_valid_hint - 1;
-        } else {
-            // no hint: ONE 4-byte read of the batch minimum of `jmin` — the only host wait of car_generate (it also waits for whatever the caller had queued before)
-            car_launch_min_int(jmin, b, jmin_min, -1, nullptr, st);
-            HIPCHK(c, hipMemcpyAsync(&hmin, jmin_min, 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-        }
-        // The window starts on a multiple of 16: a key keeps its slot inside the 16-wide k-blocks of the P·V product (one MFMA chain over the k-blocks in order:
-        // leading all-zero blocks add exact zeros), and the row softmax sums a column in the lane of its ABSOLUTE position (softmax_wave_kernel) — so a valid row's
-        // K / V rows and logits are the same bits whatever the batch-mates' prompt lengths make of t0 (tests/test_parity_gpu.py::test_exact_mode_prefill_window_invariance).
-        const int hm = hmin < 0 ? 0 : (hmin > T ? T : hmin);
-        t0 = (hm / 16) * 16; if (t0 > T - 8) t0 = ((T - 8) / 16) * 16; if (t0 < 0) t0 = 0;
-        Tv = T - t0;
-        if (Tv % 8) { Tv = T; t0 = 0; }
-        if (hinted && t0 > 0) {
-            if (!c->host_flags) { HIPCHK(c, hipHostMalloc((void**)&c->host_flags, 64, hipHostMallocMapped)); memset(c->host_flags, 0, 64); }
-            car_launch_min_int(jmin, b, jmin_min, t0, c->host_flags + 1, st);
-        }
-    }
+    if (emb_mask && !c2i && prompt_has_window(T) && (fast || T <= 128) && !CAR_KNOB("CAR_NO_PREFILL_WINDOW") &&
+        prompt_window(c, sp->first_valid_hint, jmin, b, jmin_min, T, 16, &t0, &Tv, st)) return -1;
     const unsigned char* pmask = (const unsigned char*)c->maskb.p;             // the prefill's mask: [b][Tv]
     if (t0 > 0) {
         NEED(c, c->maskw, (size_t)b * Tv);
         HIPCHK(c, hipMemcpy2DAsync(c->maskw.p, (size_t)Tv, (const unsigned char*)c->maskb.p + t0, (size_t)T, (size_t)Tv, (size_t)b, hipMemcpyDeviceToDevice, st));
         pmask = (const unsigned char*)c->maskw.p;
     }
-    const long rowsW = (long)b * Tv;                                           // rows the prefill computes (rowsP = b * T sized the buffers)
     for (int i = 0; i < 8; ++i) { c->h_init[2 * i] = T + c->dbg_skip; c->h_init[2 * i + 1] = c->dbg_skip; }    // (pos, step) per chain: after prefill the first decode step runs at input_pos = T, sampling token index 1 (+ the profiling skip)
     car_launch_set_pos_step(pos, c->h_init[0], c->h_init[1], st);
 
     // ---- D. text prefix embed: cls_embedding.cap_proj (gpt_t2i.py:435), uncond rows = uncond_embedding (generate.py:157)
-    void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *att = c->ws[8].p;
-    float* logits = (float*)c->ws[9].p;
+    void *h = c->ws[WS_H].p, *xn = c->ws[WS_XN].p, *qkv = c->ws[WS_QKV].p, *mid = c->ws[WS_MID].p, *att = c->ws[WS_ATT_OUT].p;
+    float* logits = (float*)c->ws[WS_LOGITS].p;
     if (c2i) {
         // LabelEmbedder (gpt.py:89-96): h[b] = embedding_table[label]; CFG rows use the null class num_classes (generate.py:141).
         // The row -> table-index map is built on the device (no host round trip): an out-of-range label is clamped to the null class and
         // raises a sticky device flag that car_get_stats reports (the reference's nn.Embedding fails asynchronously on a GPU as well).
         c->h_rowunc.assign(row_unc.begin(), row_unc.end());
         NEED(c, c->rowunc, (size_t)b * 4 + 16);
-        if (!c->host_flags) { HIPCHK(c, hipHostMalloc((void**)&c->host_flags, 64, hipHostMallocMapped)); memset(c->host_flags, 0, 64); }
+        if (ensure_host_flags(c)) return -1;
         HIPCHK(c, hipMemcpyAsync(c->rowunc.p, c->h_rowunc.data(), (size_t)b * 4, hipMemcpyHostToDevice, st));
         int* didx = cur;       // cur_tok[b] is free until the prefill sampler writes it
         car_launch_label_index(labels, (const int*)c->rowimg.p, (const int*)c->rowunc.p, g.num_classes, didx, c->host_flags, b, st);
         car_launch_gather_rows(mode, Wp(c, "cls_embedding.embedding_table.weight"), didx, h, b, D, st);
-    } else {
-        const long per_src = (long)T * g.caption_dim, per = (long)Tv * g.caption_dim; const size_t ib = text_dtype == CAR_DT_BF16 ? 2 : 4;
-        for (int gi = 0; gi < NG; ++gi)
-            car_launch_build_text(mode, (const char*)text_emb + (size_t)img0[gi] * per_src * ib, text_dtype, Wp(c, "cls_embedding.uncond_embedding"),
-                                  off(text, (size_t)mult * img0[gi] * per, e), img0[gi + 1] - img0[gi], per, per_src, (long)t0 * g.caption_dim, use_cfg, st);
-        mlp_tanh(c, text, g.caption_dim, 0, 1, (int)rowsW, g.caption_dim, "cls_embedding.cap_proj.", xn, h, D, st);
-    }
-    // ---- C. control tokens: condition_mlp then 3 condition_layers, cached for the whole call (gpt_t2i.py:437-442)
+    } else prompt_text(c, text_emb, text_dtype, img0, NG, use_cfg, t0, Tv, h, st);
+    // ---- C. control tokens of every chain, cached for the whole call
     if (use_control) {
-        const int Mc = B * n_tok;
-        void* ce = c->ws[11].p;
-        // scratch for the MLP hidden activations: ws[4], idle until the prefill's attention (which may need it larger)
-        DevBuf& scratch = c->ws[4];
-        NEED(c, scratch, std::max((size_t)Mc * D * e, ab.S));
-        mlp_tanh(c, c->ctrl_in.p, D, 0, 1, Mc, D, "condition_mlp.cap_proj.", scratch.p, ce, D, st);
-        for (int k = 0; k < 3; ++k) for (int gi = 0; gi < NG; ++gi) {
-            const int ng = img0[gi + 1] - img0[gi]; const size_t rows = (size_t)ng * n_tok, base = (size_t)mult * img0[gi] * n_tok;
-            mlp_tanh(c, off(ce, (size_t)img0[gi] * n_tok * D, e), D, 0, 1, (int)rows, D, "condition_layers." + std::to_string(k) + ".", scratch.p,
-                     off(c->ctrl[k].p, base * D, e), D, st);
-            if (use_cfg) HIPCHK(c, hipMemsetAsync(off(c->ctrl[k].p, (base + rows) * D, e), 0, rows * D * e, st));   // uncond rows: MLP(0) = 0 exactly
-            // row mode: image i's conditional tokens become c' = rnd(cs_i * c) once, here; prefill and decode then add rnd(1 * c') == c' (the unconditional half stays
-            // exact zeros).  Launched only when some row asks for a strength other than 1.
-            if (row_strength) car_launch_ctrl_scale_rows(mode, off(c->ctrl[k].p, base * D, e), rows_dev + img0[gi], ng, (long)n_tok * D, st);
-        }
+        NEED(c, c->ws[WS_ATTN_S], std::max((size_t)B * n_tok * D * e, ab.S));      // the control MLPs' scratch, idle until the prefill's attention (which may need it larger)
+        if (prompt_control_tokens(c, img0, NG, use_cfg, row_strength ? rows_dev : nullptr, st)) return -1;
     }
-    // ---- E. prefill over the prefix rows of the window [t0, T) (gpt_t2i.py:446-470)
-    for (int l = 0; l < g.n_layer; ++l) {
-        const std::string L = "layers." + std::to_string(l) + ".";
-        {
-            NormP np; memset(&np, 0, sizeof(np));
-            np.h_in = h; np.h_out = h; np.xn = xn; np.w = Wp(c, L + "attention_norm.weight"); np.D = D; np.eps = g.norm_eps;
-            if (use_control && l % li == 0 && l / li < 3) { np.add_mode = 2; np.ctrl = c->ctrl[l / li].p; np.T = Tv; np.n_tok = n_tok; np.cs = cs; }
-            car_launch_rmsnorm(mode, &np, rowsW, st);
-        }
-        { GemmP q = gp(xn, D, Wp(c, L + "attention.wqkv.weight"), D, qkv, 3 * D, (int)rowsW, 3 * D, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
-        if (fast) car_launch_prefill_rope_kv2(qkv, off(c->kv.p, (size_t)(2 * l) * kv_layer, kv_e), off(c->kv.p, (size_t)(2 * l + 1) * kv_layer, kv_e), c->rope, b, Tv, Hn, D, SA, g.kv_cache_fp8 ? 1 : 0, t0, st);
-        else car_launch_prefill_rope_kv(mode, qkv, off(c->kv.p, (size_t)(2 * l) * kv_layer, e), off(c->kv.p, (size_t)(2 * l + 1) * kv_layer, e), c->rope, b, Tv, Hn, D, S_max, t0, st);
-        {   // causal + pad mask over the window's columns [t0, T); q | k | v packed in the wqkv output
-            const AttnCall at = {qkv, off(qkv, (size_t)D, e), off(qkv, (size_t)2 * D, e), 3 * D, att, b, Tv, Hn, 64, 0.125f, ATTN_CAUSAL, pmask, nullptr, t0};
-            if (attn_run(c, at, st)) FAIL(c, "car_generate: the fused attention kernel rejected the prefill's shape (dim=%d, rows per sequence=%d)", D, Tv);
-        }
-        gpt_layer_tail(c, L, h, xn, att, mid, rowsW, st);
-    }
-    // final norm + logits for the LAST prefix row only (generate.py:60 samples logits[:, -1])
-    { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, "norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rowsW, st); }
+    // ---- E. prefill over the prefix rows of the window [t0, T) (gpt_t2i.py:446-470): the control token 0 lands on every sequence's last row (add_mode 2), and
+    // the rope step writes the rotated K and V rows into the cache
+    PromptPass pp = {h, xn, qkv, att, mid, b, Tv, pmask, t0, use_control ? 2 : 0, 0, 0, cs, nullptr};
+    if (fast) pp.rope = [&](int l) { car_launch_prefill_rope_kv2(qkv, off(c->kv.p, (size_t)(2 * l) * kv_layer, kv_e), off(c->kv.p, (size_t)(2 * l + 1) * kv_layer, kv_e), c->rope, b, Tv, Hn, D, SA, g.kv_cache_fp8 ? 1 : 0, t0, st); };
+    else pp.rope = [&](int l) { car_launch_prefill_rope_kv(mode, qkv, off(c->kv.p, (size_t)(2 * l) * kv_layer, e), off(c->kv.p, (size_t)(2 * l + 1) * kv_layer, e), c->rope, b, Tv, Hn, D, S_max, t0, st); };
+    if (prompt_layers(c, pp, st)) FAIL(c, "car_generate: the fused attention kernel rejected the prefill's shape (dim=%d, rows per sequence=%d)", D, Tv);
+    // logits for the LAST prefix row only (generate.py:60 samples logits[:, -1])
     { GemmP q = gp(off(xn, (size_t)(Tv - 1) * D, e), (long)Tv * D, Wp(c, "output.weight"), D, logits, V, b, V, D); q.out_f32 = 1; car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
     SampleP spp; memset(&spp, 0, sizeof(spp));
     spp.logits = logits; spp.B = B; spp.V = V; spp.use_cfg = use_cfg; spp.cfg_scale = sp->cfg_scale; spp.cfg_interval = sp->cfg_interval;
@@ -607,7 +545,7 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
 
     // ---- F/G. decode loop: one captured step, replayed n_new-1 times (pos/step/token live on the device)
     StepBufs sb; memset(&sb, 0, sizeof(sb));
-    sb.h = h; sb.xn = xn; sb.qkv = qkv; sb.att = att; sb.mid = mid; sb.part = (float*)c->ws[10].p; sb.logits = logits; sb.cur = cur;
+    sb.h = h; sb.xn = xn; sb.qkv = qkv; sb.att = att; sb.mid = mid; sb.part = (float*)c->ws[WS_PARTS].p; sb.logits = logits; sb.cur = cur;
     sb.b = b; sb.SA = SA; sb.n_tok = n_tok; sb.use_ctrl = use_control != 0; sb.cs = cs;
     sb.maskb = emb_mask ? (const unsigned char*)c->maskb.p : nullptr; sb.jmin = emb_mask ? jmin : nullptr;      // no text-pad mask: nothing to test per position
     c->stats.graph_used = 0;
@@ -670,7 +608,7 @@ static int generate_impl(car_ctx* c, const void* text_emb, int32_t text_dtype, c
         gs.cfg_interval = spp.cfg_interval; gs.sample_logits = spp.stochastic; gs.cs = cs; gs.cfg_scale = spp.cfg_scale; gs.row_mode = rows ? 1 : 0; gs.rows = rows_dev;
         gs.alloc_gen = g_alloc_gen;
         gs.kv = c->kv.p; gs.h = h; gs.xn = xn; gs.att = att; gs.mid = mid; gs.logits = logits; gs.ctrl0 = c->ctrl[0].p; gs.maskb = c->maskb.p;
-        gs.parts = c->dec_parts.p ? c->dec_parts.p : c->ws[10].p; gs.scal = c->scal.p; gs.forced = forced_tokens; gs.logits_out = logits_out;
+        gs.parts = c->dec_parts.p ? c->dec_parts.p : c->ws[WS_PARTS].p; gs.scal = c->scal.p; gs.forced = forced_tokens; gs.logits_out = logits_out;
         std::string key((const char*)&pl, sizeof(pl)); key.append((const char*)&gs, sizeof(gs));
         // capture `k` steps into `ex` unless the cached exec already holds exactly this configuration
         auto get_exec = [&](hipGraphExec_t& ex, std::string& exkey, int k, bool early = false) -> bool {

@@ -1,6 +1,7 @@
 // engine_internal.h — what the translation units of the host side share (engine.hip: lifecycle / stats / standalone sampler; engine_weights.hip: weight
-// packing, finalize, the packed-image cache; engine_attn.hip: the batched multi-head attention every transformer stage calls (attn_bytes / attn_run) and the
-// GPT layer tail shared by the prefill and car_score; engine_encode.hip: resize tables, the control encoder, Canny; engine_generate.hip: prefill, the decode
+// packing, finalize, the packed-image cache; engine_attn.hip: the batched multi-head attention every transformer stage calls (attn_bytes / attn_run);
+// engine_prompt.hip: the prompt pass shared by car_generate's prefill and car_score (the prefill window, control tokens, text prefix, the layers over the prompt
+// rows); engine_encode.hip: resize tables, the control encoder, Canny; engine_generate.hip: the prefill's row layout, the decode
 // step, generate; engine_score.hip: car_score; engine_t5.hip: the caption encoder; engine_clip.hip: the CLIP score; engine_vq.hip: VQ encode / decode;
 // engine_depth.hip, engine_hed.hip, engine_lineart.hip: the control extractors; engine_lpips.hip: LPIPS, PSNR and the tokenizer script's quantiser; engine_fid.hip: the evaluator's statistics (FID moments, precision / recall, Inception Score); engine_resize.hip, engine_metrics.hip).  Round 4 cut the single 1900-line
 // engine.hip along its stage banners: no behaviour change.  Everything here is internal: the C ABI is include/controlar_hip.h.
@@ -13,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -119,6 +121,11 @@ struct ResampleAxis {
     DevBuf d_kk, d_bounds;
 };
 
+// The slots of car_ctx::ws that the GPT path (engine_prompt / engine_generate / engine_score) and attn_run's callers agree on; every other file's use of
+// ws[] is private to it.  Two double uses: WS_ATTN_S is the control-MLP scratch before the attention needs it (prompt_control_tokens), and WS_LOGITS is
+// car_score's window scratch (it has no logits rows).
+enum WsSlot { WS_TEXT = 0, WS_H, WS_XN, WS_QKV, WS_ATTN_S, WS_ATTN_P, WS_ATTN_VT, WS_MID, WS_ATT_OUT, WS_LOGITS, WS_PARTS, WS_CTRL_MLP };
+
 struct Wt { void* p = nullptr; std::vector<int64_t> shape; int64_t numel = 0; size_t bytes = 0; };
 
 struct car_ctx {
@@ -140,7 +147,7 @@ struct car_ctx {
     int ctrl_B = 0, ctrl_ntok = 0;
     DevBuf ctrl[3];      // cached control tokens [b, n_tok, dim]
     DevBuf kv;           // [n_layer][2][b, H, S_max, 64]
-    DevBuf ws[12];       // scratch
+    DevBuf ws[12];       // scratch (the slots the GPT path and attn_run share: enum WsSlot above)
     DevBuf dec_parts;    // split-K partials of the decode linears (fp32)
     DevBuf scal;         // device ints: pos, step, cur_tok[b]
     DevBuf tok_out;      // [B, n_new] int32
@@ -198,6 +205,10 @@ static inline int check_sticky(car_ctx* c) {
     if (f[2]) { f[2] = 0; FAIL(c, "car_score: an earlier call on this context received a token id outside [0, %d) (read as token 0 on the device): its results are invalid", c->cfg.vocab_size); }
     if (f[3]) { f[3] = 0; FAIL(c, "car_clip_encode_text: an earlier call on this context received a token id outside [0, %d) (read as token 0 on the device): its embeddings are invalid", c->clip.vocab_size); }
     if (f[0]) { f[0] = 0; FAIL(c, "car_generate_c2i: an earlier call on this context received a class label outside [0, %d] (clamped to the null class on the device): its tokens are invalid", c->cfg.num_classes); }
+    return 0;
+}
+static inline int ensure_host_flags(car_ctx* c) {      // allocated by the first entry that can raise a flag
+    if (!c->host_flags) { HIPCHK(c, hipHostMalloc((void**)&c->host_flags, 64, hipHostMallocMapped)); memset(c->host_flags, 0, 64); }
     return 0;
 }
 #define NEED(ctx, buf, bytes) do { if (!(buf).ensure(bytes)) FAIL(ctx, "out of device memory allocating %zu bytes (%s:%d)", (size_t)(bytes), __FILE__, __LINE__); } while (0)
@@ -298,7 +309,7 @@ static inline bool use_flash(const car_ctx* c, int head_dim) {
 }
 
 // engine_attn.hip — multi-head attention over [nb, T, H*hd] rows.  q, k, v: row stride `ld` elements (the width for separate planes, 3 * width for the packed
-// wqkv output), sequence stride T * ld, head h at column h * hd; out: dense [nb, T, H*hd].  Scratch: ws[4] S (fp32 scores), ws[5] P, ws[6] V^T (keys zero padded
+// wqkv output), sequence stride T * ld, head h at column h * hd; out: dense [nb, T, H*hd].  Scratch: ws[WS_ATTN_S] (fp32 scores), ws[WS_ATTN_P], ws[WS_ATTN_VT] (V^T, keys zero padded
 // to a multiple of 32), which the caller sizes with attn_bytes for its largest chunk; S and P are 0 bytes when the fused kernel runs (use_flash).
 enum { ATTN_NONE = 0, ATTN_CAUSAL = 1, ATTN_T5 = 2 };      // = FlashP::mode: no mask | causal + pad mask [nb][T], window starting at column col0 | bias [H][T][T] + key mask [nb][T]
 struct AttnCall {
@@ -309,7 +320,22 @@ struct AttnCall {
 struct AttnBytes { size_t S, P, Vt; };
 AttnBytes attn_bytes(const car_ctx* c, int nb, int T, int H, int hd);
 int attn_run(car_ctx* c, const AttnCall& a, hipStream_t st);      // non-zero: the fused kernel refused the shape, nothing further was launched — fail the call
-void gpt_layer_tail(car_ctx* c, const std::string& L, void* h, void* xn, const void* att, void* mid, long rows, hipStream_t st);
+
+// engine_prompt.hip — the prompt pass of car_generate (its prefill) and car_score.  Row group g = images [img0[g], img0[g+1]), rows [cond | uncond] under CFG:
+// car_generate's groups are its decode chains, car_score's are its chunks.
+static inline bool prompt_has_window(int T) { return T > 8 && T % 8 == 0; }      // the window rule (engine_prompt.hip) gives any other T all its rows
+int prompt_window(car_ctx* c, int hint, const int* jmin, int n, int* jmin_min, int T, int grain, int* t0, int* Tv, hipStream_t st);
+int prompt_control_tokens(car_ctx* c, const int* img0, int n_groups, bool use_cfg, const SampleRow* strength_rows, hipStream_t st);
+void prompt_text(car_ctx* c, const void* text_emb, int text_dtype, const int* img0, int n_groups, bool use_cfg, int t0, int Tv, void* out, hipStream_t st);
+struct PromptPass {
+    void *h, *xn, *qkv, *att, *mid;                  // nseq * Tn rows each (mid: gpt_layer_tail's sizing); h holds the input rows
+    int nseq, Tn;                                    // sequences, rows per sequence
+    const unsigned char* mask; int col0;             // pad mask [nseq][Tn] and the prompt column of its first one (the window start)
+    int add_mode, ctrl_row0; size_t ctrl_off; float cs;      // the control add of rmsnorm (kernel_params.h NormP; add_mode 0: no control): first row that takes a token,
+                                                     // element offset of the pass's first sequence in c->ctrl[k], strength
+    std::function<void(int layer)> rope;             // the step between wqkv and the attention: RoPE on qkv in place, with or without the KV-cache write
+};
+int prompt_layers(car_ctx* c, const PromptPass& p, hipStream_t st);
 
 // y = fc2(gelu_tanh(fc1 x))   (gpt_t2i.py:165-181), x: [z][M, K] with row stride lda / batch stride sA
 static inline void mlp_tanh(car_ctx* c, const void* x, long lda, long sA, int nb, int M, int K, const std::string& pfx, void* mid, void* y, int dim, hipStream_t st) {

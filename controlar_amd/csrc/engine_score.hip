@@ -3,7 +3,7 @@
 // (one of the translation units behind include/controlar_hip.h; shared declarations: engine_internal.h)
 //
 // The causal structure makes the logits of all n_new positions computable from ONE pass over Ts = Tv + n_new - 1 rows per sequence: the Tv rows of the
-// prefix window (as car_generate's prefill, engine_generate.hip stage E) followed by the embeddings of tokens[:, :n_new-1]; the logits row that generate()
+// prefix window (as car_generate's prefill: the prompt pass of engine_prompt.hip) followed by the embeddings of tokens[:, :n_new-1]; the logits row that generate()
 // hands to sample() at step i is the output of sequence row Tv - 1 + i.  Stages C (control tokens) and D (text prefix) and the layer loop are the prefill's,
 // on the same generic GEMMs (row-count agnostic; every output element sums its k-blocks in order whatever M), with three differences: the control token j is
 // added on row Tv - 1 + j at layers 0, n/3, 2n/3 (rmsnorm add_mode 3; the unconditional half adds exact zeros), RoPE runs in place without a KV cache
@@ -29,11 +29,6 @@ void car_launch_score_mask(const int64_t* emb_mask, unsigned char* out, int nseq
 
 enum { kScoreRows = 16384 };                      // activation rows per chunk (the chunk rule above)
 static const size_t kScoreTensorCap = (size_t)1 << 30;
-
-static int ensure_host_flags(car_ctx* c) {
-    if (!c->host_flags) { HIPCHK(c, hipHostMalloc((void**)&c->host_flags, 64, hipHostMallocMapped)); memset(c->host_flags, 0, 64); }
-    return 0;
-}
 
 extern "C" int car_score(car_ctx* c, const void* text_emb, int32_t text_dtype, const int64_t* emb_mask, int32_t B, int32_t n_new, int32_t use_control,
                          const car_sampling* sp, const int32_t* tokens, float* nll_out, float* logits_out, void* stream_) {
@@ -64,7 +59,7 @@ extern "C" int car_score_rows(car_ctx* c, const void* text_emb, int32_t text_dty
     const float cs = (use_cfg && !trows) ? sp->control_strength : 1.0f;         // generate.py:87-92: strength ignored when cfg <= 1
     bool row_strength = false;
     if (trows && use_cfg && use_control) for (int i = 0; i < B; ++i) row_strength |= trows[i].control_strength != 1.0f;
-    const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok, li = g.n_layer / 3;
+    const int D = g.dim, Hn = g.n_head, Fh = g.ffn_hidden, V = g.vocab_size, n_tok = c->ctrl_ntok;
     const int mode = c->mode; const size_t e = c->esz; const bool fast = mode == CAR_BF16;
     if (D != Hn * 64) FAIL(c, "car_score: heads must be 64 wide");
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
@@ -84,25 +79,13 @@ extern "C" int car_score_rows(car_ctx* c, const void* text_emb, int32_t text_dty
     }
     // ---- the prefill window of car_generate on the valid tail of the left-padded prompts, its start a multiple of 32 (see the chunk rule)
     int Tv = T, t0 = 0;
-    if (emb_mask && T > 8 && T % 8 == 0 && (fast || T <= 128)) {
-        // scratch of its own (ws[9], the token loop's logits buffer, idle here): car_generate's device scalars stay as its car_get_stats expects them
-        NEED(c, c->ws[9], (size_t)(B + 4) * 4 + (size_t)B * T);
-        int* jmin = (int*)c->ws[9].p; int* jmin_min = jmin + B; unsigned char* mask_all = (unsigned char*)(jmin_min + 4);
+    if (emb_mask && prompt_has_window(T) && (fast || T <= 128)) {
+        // scratch of its own (ws[WS_LOGITS], the token loop's logits buffer, idle here): car_generate's device scalars stay as its car_get_stats expects them
+        NEED(c, c->ws[WS_LOGITS], (size_t)(B + 4) * 4 + (size_t)B * T);
+        int* jmin = (int*)c->ws[WS_LOGITS].p; int* jmin_min = jmin + B; unsigned char* mask_all = (unsigned char*)(jmin_min + 4);
         car_launch_score_mask(emb_mask, mask_all, B, B, 0, T, 0, T, T, st);      // [B][T]: the whole prefix of every image
         car_launch_mask_first_valid(mask_all, jmin, B, T, st);
-        int hmin = 0;
-        const bool hinted = sp->first_valid_hint > 0;
-        if (hinted) hmin = sp->first_valid_hint - 1;
-        else {      // no hint: ONE 4-byte read of the batch minimum, the call's only host wait (as car_generate)
-            car_launch_min_int(jmin, B, jmin_min, -1, nullptr, st);
-            HIPCHK(c, hipMemcpyAsync(&hmin, jmin_min, 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-        }
-        const int hm = hmin < 0 ? 0 : (hmin > T ? T : hmin);
-        t0 = (hm / 32) * 32; if (t0 > T - 8) t0 = ((T - 8) / 32) * 32; if (t0 < 0) t0 = 0;
-        Tv = T - t0;
-        if (Tv % 8) { Tv = T; t0 = 0; }
-        if (hinted && t0 > 0) car_launch_min_int(jmin, B, jmin_min, t0, c->host_flags + 1, st);
+        if (prompt_window(c, sp->first_valid_hint, jmin, B, jmin_min, T, 32, &t0, &Tv, st)) return -1;
     }
     const int Ts = Tv + n_new - 1;
     int nc = kScoreRows / (mult * Ts); if (nc < 1) nc = 1; if (nc > B) nc = B;
@@ -113,66 +96,42 @@ extern "C" int car_score_rows(car_ctx* c, const void* text_emb, int32_t text_dty
     const int nparts = car_score_nparts(V);
 
     // ---- buffers (the prefill's workspaces, sized for one chunk)
-    NEED(c, c->ws[0], (size_t)bc * Tv * g.caption_dim * e);
-    NEED(c, c->ws[1], (size_t)rowsC * D * e);
-    NEED(c, c->ws[2], (size_t)rowsC * D * e);
-    NEED(c, c->ws[3], (size_t)rowsC * 3 * D * e);
+    NEED(c, c->ws[WS_TEXT], (size_t)bc * Tv * g.caption_dim * e);
+    NEED(c, c->ws[WS_H], (size_t)rowsC * D * e);
+    NEED(c, c->ws[WS_XN], (size_t)rowsC * D * e);
+    NEED(c, c->ws[WS_QKV], (size_t)rowsC * 3 * D * e);
     const AttnBytes ab = attn_bytes(c, bc, Ts, Hn, 64);
-    { const size_t s4 = std::max(use_control ? (size_t)B * n_tok * D * e : 0, ab.S); if (s4) NEED(c, c->ws[4], s4); }      // control-MLP scratch, then S
-    if (ab.P) NEED(c, c->ws[5], ab.P);
-    NEED(c, c->ws[6], ab.Vt);
-    NEED(c, c->ws[7], (size_t)rowsC * (fast ? Fh : 3 * Fh) * e);
-    NEED(c, c->ws[8], (size_t)rowsC * D * e);
-    NEED(c, c->ws[10], (size_t)nparts * nc * n_new * 16);
+    { const size_t s4 = std::max(use_control ? (size_t)B * n_tok * D * e : 0, ab.S); if (s4) NEED(c, c->ws[WS_ATTN_S], s4); }      // control-MLP scratch, then S
+    if (ab.P) NEED(c, c->ws[WS_ATTN_P], ab.P);
+    NEED(c, c->ws[WS_ATTN_VT], ab.Vt);
+    NEED(c, c->ws[WS_MID], (size_t)rowsC * (fast ? Fh : 3 * Fh) * e);
+    NEED(c, c->ws[WS_ATT_OUT], (size_t)rowsC * D * e);
+    NEED(c, c->ws[WS_PARTS], (size_t)nparts * nc * n_new * 16);
     NEED(c, c->maskw, (size_t)bc * Ts);
-    if (use_control) { NEED(c, c->ws[11], (size_t)B * n_tok * D * e); for (int k = 0; k < 3; ++k) NEED(c, c->ctrl[k], (size_t)b * n_tok * D * e); }
-    void *text = c->ws[0].p, *h = c->ws[1].p, *xn = c->ws[2].p, *qkv = c->ws[3].p, *mid = c->ws[7].p, *att = c->ws[8].p;
+    if (use_control) { NEED(c, c->ws[WS_CTRL_MLP], (size_t)B * n_tok * D * e); for (int k = 0; k < 3; ++k) NEED(c, c->ctrl[k], (size_t)b * n_tok * D * e); }
+    void *h = c->ws[WS_H].p, *xn = c->ws[WS_XN].p, *qkv = c->ws[WS_QKV].p, *mid = c->ws[WS_MID].p, *att = c->ws[WS_ATT_OUT].p;
 
-    // ---- C. control tokens of every chunk: condition_mlp, then the 3 condition_layers (gpt_t2i.py:437-442); rows [cond | zeros] per chunk
-    if (use_control) {
-        void* ce = c->ws[11].p; void* scratch = c->ws[4].p;
-        mlp_tanh(c, c->ctrl_in.p, D, 0, 1, B * n_tok, D, "condition_mlp.cap_proj.", scratch, ce, D, st);
-        for (int k = 0; k < 3; ++k) for (int i0 = 0; i0 < B; i0 += nc) {
-            const int ng = std::min(nc, B - i0); const size_t rows = (size_t)ng * n_tok, base = (size_t)mult * i0 * n_tok;
-            mlp_tanh(c, off(ce, (size_t)i0 * n_tok * D, e), D, 0, 1, (int)rows, D, "condition_layers." + std::to_string(k) + ".", scratch, off(c->ctrl[k].p, base * D, e), D, st);
-            if (use_cfg) HIPCHK(c, hipMemsetAsync(off(c->ctrl[k].p, (base + rows) * D, e), 0, rows * D * e, st));   // uncond rows: MLP(0) = 0 exactly
-            if (row_strength) car_launch_ctrl_scale_rows(mode, off(c->ctrl[k].p, base * D, e), rows_dev + i0, ng, (long)n_tok * D, st);   // row mode: c' = rnd(cs_i * c), once
-        }
-    }
-    const long per_src = (long)T * g.caption_dim, per = (long)Tv * g.caption_dim; const size_t ib = text_dtype == CAR_DT_BF16 ? 2 : 4;
+    std::vector<int> chunk0;      // chunk ci = images [chunk0[ci], chunk0[ci + 1])
+    for (int i0 = 0; i0 < B; i0 += nc) chunk0.push_back(i0);
+    chunk0.push_back(B);
+    const int n_chunks = (int)chunk0.size() - 1;
+    // ---- C. control tokens of every chunk; rows [cond | zeros] per chunk
+    if (use_control && prompt_control_tokens(c, chunk0.data(), n_chunks, use_cfg, row_strength ? rows_dev : nullptr, st)) return -1;
     int rc = 0;
-    for (int i0 = 0; i0 < B; i0 += nc) {
-        const int ng = std::min(nc, B - i0), nseq = mult * ng; const long rows = (long)nseq * Ts, rowsW = (long)nseq * Tv;
-        // ---- D. input rows: the window of the text prefix (cls_embedding.cap_proj, gpt_t2i.py:435; uncond rows = uncond_embedding), then the token embeddings
-        car_launch_build_text(mode, (const char*)text_emb + (size_t)i0 * per_src * ib, text_dtype, Wp(c, "cls_embedding.uncond_embedding"), text, ng, per, per_src,
-                              (long)t0 * g.caption_dim, use_cfg, st);
-        mlp_tanh(c, text, g.caption_dim, 0, 1, (int)rowsW, g.caption_dim, "cls_embedding.cap_proj.", xn, att, D, st);
+    for (int ci = 0; ci < n_chunks; ++ci) {
+        const int i0 = chunk0[ci], ng = chunk0[ci + 1] - i0, nseq = mult * ng;
+        // ---- D. input rows: the window of the text prefix in the first Tv rows of every sequence, then the token embeddings
+        prompt_text(c, text_emb, text_dtype, &chunk0[ci], 1, use_cfg, t0, Tv, att, st);
         HIPCHK(c, hipMemcpy2DAsync(h, (size_t)Ts * D * e, att, (size_t)Tv * D * e, (size_t)Tv * D * e, (size_t)nseq, hipMemcpyDeviceToDevice, st));
         car_launch_score_embed(mode, Wp(c, "tok_embeddings.weight"), tokens + (size_t)i0 * n_new, h, nseq, ng, n_new, Ts, Tv, D, V, err_flag, st);
         car_launch_score_mask(emb_mask, (unsigned char*)c->maskw.p, nseq, ng, i0, T, t0, Tv, Ts, st);
-        const unsigned char* maskx = (const unsigned char*)c->maskw.p;
-        // ---- E. the layers over all Ts rows (gpt_t2i.py:446-470)
-        for (int l = 0; l < g.n_layer; ++l) {
-            const std::string L = "layers." + std::to_string(l) + ".";
-            {
-                NormP np; memset(&np, 0, sizeof(np));
-                np.h_in = h; np.h_out = h; np.xn = xn; np.w = Wp(c, L + "attention_norm.weight"); np.D = D; np.eps = g.norm_eps;
-                if (use_control && l % li == 0 && l / li < 3) {
-                    np.add_mode = 3; np.ctrl = off(c->ctrl[l / li].p, (size_t)mult * i0 * n_tok * D, e); np.T = Ts; np.row0 = Tv - 1; np.n_tok = n_tok; np.cs = cs;
-                }
-                car_launch_rmsnorm(mode, &np, rows, st);
-            }
-            { GemmP q = gp(xn, D, Wp(c, L + "attention.wqkv.weight"), D, qkv, 3 * D, (int)rows, 3 * D, D); car_launch_gemm(mode, AMODE_PLAIN, &q, st); }
-            car_launch_score_rope(mode, qkv, c->rope, nseq, Ts, Hn, D, t0, st);
-            const AttnCall at = {qkv, off(qkv, (size_t)D, e), off(qkv, (size_t)2 * D, e), 3 * D, att, nseq, Ts, Hn, 64, 0.125f, ATTN_CAUSAL, maskx, nullptr, t0};
-            if (attn_run(c, at, st)) { rc = -2; break; }      // flash64 takes every shape this pass builds (engine_attn.hip)
-            gpt_layer_tail(c, L, h, xn, att, mid, rows, st);
-        }
-        if (rc) break;
-        { NormP np; memset(&np, 0, sizeof(np)); np.h_in = h; np.xn = xn; np.w = Wp(c, "norm.weight"); np.D = D; np.eps = g.norm_eps; car_launch_rmsnorm(mode, &np, rows, st); }
+        // ---- E. the layers over all Ts rows: control token j lands on row Tv - 1 + j (add_mode 3), and RoPE runs in place (no KV cache)
+        PromptPass pp = {h, xn, qkv, att, mid, nseq, Ts, (const unsigned char*)c->maskw.p, t0, use_control ? 3 : 0, Tv - 1, (size_t)mult * i0 * n_tok * D, cs,
+                         [&](int) { car_launch_score_rope(mode, qkv, c->rope, nseq, Ts, Hn, D, t0, st); }};
+        if (prompt_layers(c, pp, st)) { rc = -2; break; }
         // ---- the loss: rows Tv - 1 + i of every sequence against output.weight, the CFG pair mixed on the accumulators (score.hip)
         ScoreP p; memset(&p, 0, sizeof(p));
-        p.x = xn; p.w = Wp(c, "output.weight"); p.targets = tokens + (size_t)i0 * n_new; p.part = (float*)c->ws[10].p;
+        p.x = xn; p.w = Wp(c, "output.weight"); p.targets = tokens + (size_t)i0 * n_new; p.part = (float*)c->ws[WS_PARTS].p;
         p.logits = logits_out ? logits_out + (size_t)i0 * n_new * V : nullptr;
         p.ldx = D; p.seq_stride = Ts; p.row_off = Tv - 1; p.unc_off = (long)ng * Ts; p.R = ng * n_new; p.V = V; p.D = D; p.rows_per_seq = n_new;
         p.paired = use_cfg ? 1 : 0; p.round_bf16 = fast ? 1 : 0;      // fast mode: the logits are a bf16 linear's output widened to fp32 (gpt_t2i.py:470), as the decode step rounds them
@@ -198,11 +157,11 @@ extern "C" int car_debug_score_rows(car_ctx* c, const void* x, const void* w, co
     if (pair_scale && (R & 1)) FAIL(c, "car_debug_score_rows: a pair scale needs an even number of rows");
     if (ensure_host_flags(c)) return -1;
     const int Ro = pair_scale ? R / 2 : R;
-    NEED(c, c->ws[10], (size_t)car_score_nparts(V) * Ro * 16);
+    NEED(c, c->ws[WS_PARTS], (size_t)car_score_nparts(V) * Ro * 16);
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
     fence_in(c, caller);
     ScoreP p; memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.targets = targets; p.scale = pair_scale; p.part = (float*)c->ws[10].p; p.logits = logits;
+    p.x = x; p.w = w; p.targets = targets; p.scale = pair_scale; p.part = (float*)c->ws[WS_PARTS].p; p.logits = logits;
     p.ldx = D; p.seq_stride = 0; p.row_off = 0; p.unc_off = Ro; p.R = Ro; p.V = V; p.D = D; p.rows_per_seq = Ro;
     p.paired = pair_scale ? 1 : 0; p.round_bf16 = round_bf16 ? 1 : 0; p.cfg_interval = -1; p.cfg_scale = 1.f;
     const int rc = car_launch_score(c->mode, &p, nll, c->host_flags + 2, st);

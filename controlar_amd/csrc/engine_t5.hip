@@ -98,9 +98,9 @@ extern "C" int car_t5_encode(car_ctx* c, const int64_t* input_ids, const int64_t
     NEED(c, c->ws[1], (size_t)n_tok * D * e);                 // h (all rows: gathered up front)
     NEED(c, c->ws[2], (size_t)rows_max * D * e);              // xn
     NEED(c, c->ws[3], (size_t)rows_max * 3 * inner * e);      // q | k | v planes
-    if (ab.S) NEED(c, c->ws[4], ab.S);                        // S fp32: the fp32 mode, and heads that are not 64 wide
-    if (ab.P) NEED(c, c->ws[5], ab.P);                        // P
-    NEED(c, c->ws[6], ab.Vt);                                 // V^T
+    if (ab.S) NEED(c, c->ws[WS_ATTN_S], ab.S);                        // S fp32: the fp32 mode, and heads that are not 64 wide
+    if (ab.P) NEED(c, c->ws[WS_ATTN_P], ab.P);                        // P
+    NEED(c, c->ws[WS_ATTN_VT], ab.Vt);                                 // V^T
     NEED(c, c->ws[7], (size_t)rows_max * F * e);              // gated mid
     NEED(c, c->ws[8], (size_t)rows_max * inner * e);          // ctx
     if (mode == CAR_F32) NEED(c, c->ws[9], (size_t)rows_max * 2 * F * e);   // exact mode: wi_0 | wi_1 outputs before the gate

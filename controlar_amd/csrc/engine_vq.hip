@@ -94,11 +94,11 @@ struct VqOps {
                 gn(x, t1, it.name + ".norm", nb, HW, C, 0);
                 void* qb = c->ws[7].p; void* kb = off(qb, (size_t)nb * HW * C, e); void* vb = off(qb, (size_t)2 * nb * HW * C, e);
                 conv1(t1, qb, it.name + ".q", nb * HW, C, C, nullptr); conv1(t1, kb, it.name + ".k", nb * HW, C, C, nullptr); conv1(t1, vb, it.name + ".v", nb * HW, C, C, nullptr);
-                float* S = (float*)c->ws[4].p;
+                float* S = (float*)c->ws[WS_ATTN_S].p;
                 { GemmP q = gp(qb, C, kb, C, S, HW, HW, HW, C); q.alpha = 1.0f / std::sqrt((float)C); q.out_f32 = 1; q.nb0 = nb; q.sA0 = (long)HW * C; q.sW0 = (long)HW * C; q.sC0 = (long)HW * HW; q.split3 = split3; launch(AMODE_PLAIN, q); }
-                car_launch_softmax(mode, S, HW, c->ws[5].p, Tp, (long)nb * HW, HW, 0, nullptr, 0, 0, st);
-                car_launch_transpose_pad(mode, vb, C, (long)HW * C, c->ws[6].p, nb, HW, Tp, C, st);
-                { GemmP q = gp(c->ws[5].p, Tp, c->ws[6].p, Tp, t2, C, HW, C, Tp); q.nb0 = nb; q.sA0 = (long)HW * Tp; q.sW0 = (long)C * Tp; q.sC0 = (long)HW * C; q.split3 = split3; launch(AMODE_PLAIN, q); }
+                car_launch_softmax(mode, S, HW, c->ws[WS_ATTN_P].p, Tp, (long)nb * HW, HW, 0, nullptr, 0, 0, st);
+                car_launch_transpose_pad(mode, vb, C, (long)HW * C, c->ws[WS_ATTN_VT].p, nb, HW, Tp, C, st);
+                { GemmP q = gp(c->ws[WS_ATTN_P].p, Tp, c->ws[WS_ATTN_VT].p, Tp, t2, C, HW, C, Tp); q.nb0 = nb; q.sA0 = (long)HW * Tp; q.sW0 = (long)C * Tp; q.sC0 = (long)HW * C; q.split3 = split3; launch(AMODE_PLAIN, q); }
                 conv1(t2, x, it.name + ".proj_out", nb * HW, C, C, x);
             } else if (it.kind == 2) {
                 Hc *= 2; Wc *= 2;
@@ -131,9 +131,9 @@ extern "C" int car_vq_encode(car_ctx* c, const float* img, int32_t B, int32_t H,
     { size_t hw = (size_t)H * W; for (auto& it : layout) { if (it.kind == 3) hw /= 4; size_t cc = it.cin > it.cout ? it.cin : it.cout; if (hw * cc > max_el) max_el = hw * cc; } }
     int CH = B; while (CH > 1 && (size_t)CH * max_el * e * 4 > ((size_t)8 << 30)) CH = (CH + 1) / 2;
     for (int i = 0; i < 4; ++i) NEED(c, c->ws[i], (size_t)CH * max_el * e);
-    NEED(c, c->ws[4], (size_t)CH * HW0 * HW0 * 4);
-    NEED(c, c->ws[5], (size_t)CH * HW0 * HWp * e);
-    NEED(c, c->ws[6], (size_t)CH * last_c * HWp * e);
+    NEED(c, c->ws[WS_ATTN_S], (size_t)CH * HW0 * HW0 * 4);
+    NEED(c, c->ws[WS_ATTN_P], (size_t)CH * HW0 * HWp * e);
+    NEED(c, c->ws[WS_ATTN_VT], (size_t)CH * last_c * HWp * e);
     NEED(c, c->ws[7], (size_t)CH * 3 * HW0 * last_c * e);
     NEED(c, c->ws[8], (size_t)CH * ((size_t)(H * W + 255) / 256) * 2 * 512 * 4 + 1024);
     NEED(c, c->ws[9], (size_t)CH * 32 * 2 * 4 + 64);
@@ -176,9 +176,9 @@ extern "C" int car_vq_decode(car_ctx* c, const int32_t* tokens, int32_t B, int32
     for (int i = 0; i < 4; ++i) NEED(c, c->ws[i], abytes);
     const int HW0 = hh * ww, C0 = g.vq_ch * g.vq_ch_mult[g.vq_n_mult - 1];
     const int HWp = (int)rup(HW0, 32);
-    NEED(c, c->ws[4], (size_t)CH * HW0 * HW0 * 4);            // attention scores fp32
-    NEED(c, c->ws[5], (size_t)CH * HW0 * HWp * e);            // P
-    NEED(c, c->ws[6], (size_t)CH * C0 * HWp * e);             // V^T
+    NEED(c, c->ws[WS_ATTN_S], (size_t)CH * HW0 * HW0 * 4);            // attention scores fp32
+    NEED(c, c->ws[WS_ATTN_P], (size_t)CH * HW0 * HWp * e);            // P
+    NEED(c, c->ws[WS_ATTN_VT], (size_t)CH * C0 * HWp * e);             // V^T
     NEED(c, c->ws[7], (size_t)CH * 3 * HW0 * C0 * e);         // q, k, v
     NEED(c, c->ws[8], (size_t)CH * ((size_t)(Hf * Wf + 255) / 256) * 2 * 512 * 4 + 1024);   // GN partials (C <= 512)
     NEED(c, c->ws[9], (size_t)CH * 32 * 2 * 4 + 64);          // GN stats

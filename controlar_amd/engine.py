@@ -135,6 +135,21 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"{what}: {self.lib.car_last_error(self._h).decode()}")
 
+    def _prompt_mask(self, who: str, emb_masks, B: int, T: int, first_valid):
+        """The pad mask of generate / score (`who`) as a device int64 tensor, and car_sampling.first_valid_hint: the caller's `first_valid` clamped to [0, T], plus
+        one; 0 without a mask or a value.  A mask that is still on the host supplies the value for free, and a caller's value is checked against it."""
+        if emb_masks is None:
+            return None, 0
+        assert emb_masks.shape[0] == B and emb_masks.shape[-1] == T          # generate.py:185-186
+        if emb_masks.device.type == "cpu" and emb_masks.numel():
+            true_first = first_valid_position(emb_masks.reshape(B, T))
+            if first_valid is not None and int(first_valid) > true_first:
+                raise RuntimeError(f"{who}: first_valid={int(first_valid)} is beyond the first valid prompt position of the batch ({true_first}): valid rows would be dropped")
+            if first_valid is None:
+                first_valid = true_first
+        mask_t = emb_masks.to(device=self.device, dtype=torch.int64).contiguous()
+        return mask_t, (0 if first_valid is None else max(0, min(int(first_valid), T)) + 1)
+
     def close(self):
         """Destroys the context.  A device-side error that no entry could report synchronously (wrong first_valid hint, out-of-range device label) is raised here
         at the latest — after the context is gone, so that close() always releases the memory."""
@@ -221,20 +236,11 @@ class Engine:
             cond = cond.contiguous()
             B, T, cap = cond.shape
             assert T == self.cfg.gpt.cls_token_num and cap == self.cfg.gpt.caption_dim
-        mask_t = None
-        if emb_masks is not None:
-            assert emb_masks.shape[0] == B and emb_masks.shape[-1] == T          # generate.py:185-186
-            if emb_masks.device.type == "cpu" and emb_masks.numel():
-                true_first = first_valid_position(emb_masks.reshape(B, T))
-                if first_valid is not None and int(first_valid) > true_first:
-                    raise RuntimeError(f"generate: first_valid={int(first_valid)} is beyond the first valid prompt position of the batch ({true_first}): valid rows would be dropped")
-                if first_valid is None:
-                    first_valid = true_first
-            mask_t = emb_masks.to(device=self.device, dtype=torch.int64).contiguous()
+        mask_t, hint = self._prompt_mask("generate", emb_masks, B, T, first_valid)
         rows = sampling_rows(B, rng_stream, cfg_scale=cfg_scale, cfg_interval=cfg_interval, temperature=temperature, top_k=top_k, top_p=top_p,
                              sample_logits=sample_logits, seed=seed, control_strength=control_strength)
         sp = L.CarSampling()
-        sp.first_valid_hint = 0 if (first_valid is None or emb_masks is None) else max(0, min(int(first_valid), T)) + 1
+        sp.first_valid_hint = hint
         if rows is None:
             sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), float(temperature), int(top_k or 0)
             sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = float(top_p), int(bool(sample_logits)), int(seed), float(control_strength)
@@ -243,32 +249,16 @@ class Engine:
         if forced_tokens is not None:
             forced = forced_tokens.to(device=self.device, dtype=torch.int32).contiguous()
         logits = torch.empty(B, max_new_tokens, self.cfg.gpt.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
-        if rows is not None and c2i:
-            self._check(self.lib.car_generate_c2i_rows(self._h, C.c_void_p(cond.data_ptr()), B, int(max_new_tokens), int(bool(use_control)),
-                                                       C.byref(sp), rows, C.c_void_p(out.data_ptr()),
-                                                       C.c_void_p(forced.data_ptr() if forced is not None else 0),
-                                                       C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())),
-                        "car_generate_c2i_rows")
-        elif rows is not None:
-            self._check(self.lib.car_generate_rows(self._h, C.c_void_p(cond.data_ptr()), _dt(cond),
-                                                   C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0), B, int(max_new_tokens),
-                                                   int(bool(use_control)), C.byref(sp), rows, C.c_void_p(out.data_ptr()),
-                                                   C.c_void_p(forced.data_ptr() if forced is not None else 0),
-                                                   C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())),
-                        "car_generate_rows")
-        elif c2i:
-            self._check(self.lib.car_generate_c2i(self._h, C.c_void_p(cond.data_ptr()), B, int(max_new_tokens), int(bool(use_control)),
-                                                  C.byref(sp), C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(forced.data_ptr() if forced is not None else 0),
-                                                  C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())),
-                        "car_generate_c2i")
+        # the *_rows entries with rows = NULL are the plain calls (include/controlar_hip.h); errors keep the plain entry's name then
+        tail = (C.byref(sp), rows, C.c_void_p(out.data_ptr()), C.c_void_p(forced.data_ptr() if forced is not None else 0),
+                C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr()))
+        sfx = "_rows" if rows is not None else ""
+        if c2i:
+            self._check(self.lib.car_generate_c2i_rows(self._h, C.c_void_p(cond.data_ptr()), B, int(max_new_tokens), int(bool(use_control)), *tail),
+                        "car_generate_c2i" + sfx)
         else:
-            self._check(self.lib.car_generate(self._h, C.c_void_p(cond.data_ptr()), _dt(cond),
-                                              C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0), B, int(max_new_tokens),
-                                              int(bool(use_control)), C.byref(sp), C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(forced.data_ptr() if forced is not None else 0),
-                                              C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())),
-                        "car_generate")
+            self._check(self.lib.car_generate_rows(self._h, C.c_void_p(cond.data_ptr()), _dt(cond), C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0),
+                                                   B, int(max_new_tokens), int(bool(use_control)), *tail), "car_generate" + sfx)
         return (out, logits) if return_logits else out
 
     def score(self, cond: torch.Tensor, tokens: torch.Tensor, emb_masks: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
@@ -297,34 +287,21 @@ class Engine:
         if cond.dtype not in (torch.float32, torch.bfloat16):
             cond = cond.float()
         cond = cond.contiguous()
-        mask_t = None
-        if emb_masks is not None:
-            assert emb_masks.shape[0] == B and emb_masks.shape[-1] == T          # generate.py:185-186
-            if emb_masks.device.type == "cpu" and emb_masks.numel():
-                true_first = first_valid_position(emb_masks.reshape(B, T))
-                if first_valid is not None and int(first_valid) > true_first:
-                    raise RuntimeError(f"score: first_valid={int(first_valid)} is beyond the first valid prompt position of the batch ({true_first}): valid rows would be dropped")
-                if first_valid is None:
-                    first_valid = true_first
-            mask_t = emb_masks.to(device=self.device, dtype=torch.int64).contiguous()
+        mask_t, hint = self._prompt_mask("score", emb_masks, B, T, first_valid)
         rows = sampling_rows(B, None, cfg_scale=cfg_scale, cfg_interval=cfg_interval, temperature=1.0, top_k=0, top_p=1.0, sample_logits=False, seed=0,
                              control_strength=control_strength)
         sp = L.CarSampling()
-        sp.first_valid_hint = 0 if (first_valid is None or emb_masks is None) else max(0, min(int(first_valid), T)) + 1
+        sp.first_valid_hint = hint
         if rows is None:
             sp.cfg_scale, sp.cfg_interval, sp.temperature, sp.top_k = float(cfg_scale), int(cfg_interval), 1.0, 0
             sp.top_p, sp.sample_logits, sp.seed, sp.control_strength = 1.0, 0, 0, float(control_strength)
         tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
         nll = torch.empty(B, N, dtype=torch.float32, device=self.device)
         logits = torch.empty(B, N, self.cfg.gpt.vocab_size, dtype=torch.float32, device=self.device) if return_logits else None
-        if rows is not None:
-            self._check(self.lib.car_score_rows(self._h, C.c_void_p(cond.data_ptr()), _dt(cond), C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0),
-                                                B, N, int(bool(use_control)), C.byref(sp), rows, C.c_void_p(tok.data_ptr()), C.c_void_p(nll.data_ptr()),
-                                                C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())), "car_score_rows")
-            return (nll, logits) if return_logits else nll
-        self._check(self.lib.car_score(self._h, C.c_void_p(cond.data_ptr()), _dt(cond), C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0),
-                                       B, N, int(bool(use_control)), C.byref(sp), C.c_void_p(tok.data_ptr()), C.c_void_p(nll.data_ptr()),
-                                       C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())), "car_score")
+        self._check(self.lib.car_score_rows(self._h, C.c_void_p(cond.data_ptr()), _dt(cond), C.c_void_p(mask_t.data_ptr() if mask_t is not None else 0),
+                                            B, N, int(bool(use_control)), C.byref(sp), rows, C.c_void_p(tok.data_ptr()), C.c_void_p(nll.data_ptr()),
+                                            C.c_void_p(logits.data_ptr() if logits is not None else 0), C.c_void_p(_stream_ptr())),
+                    "car_score_rows" if rows is not None else "car_score")
         return (nll, logits) if return_logits else nll
 
     def score_rows(self, x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, pair_scale: Optional[torch.Tensor] = None,

@@ -616,6 +616,11 @@ int car_debug_score_rows(car_ctx* ctx, const void* x, const void* w, const int32
  * 0 if the lane holds no attended row and gets zeros instead.  Non-zero on a range outside those bounds. */
 int car_debug_attn_edge_mask(int32_t lo, int32_t hi, unsigned char* k_mask /* [4*64] */, unsigned char* v_mask /* [4*64] */);
 
+/* Host-only: the prefill window of car_generate (grain 16) and car_score (grain 32) over a prompt of T positions whose first valid (unpadded) position over
+ * the batch is first_valid: the pass computes rows [t0, T), Tv = T - t0 of them.  t0 is the largest multiple of grain that is <= min(clamp(first_valid, 0, T),
+ * T - 8); t0 = 0 unless T > 8 and T is a multiple of 8.  Non-zero on T <= 0 or a grain that is not a positive multiple of 8. */
+int car_debug_prompt_window(int32_t T, int32_t first_valid, int32_t grain, int32_t* t0, int32_t* Tv);
+
 /* Copies the cached control tokens of layer-group k (0..2) [b,n_tok,dim] as fp32 to a HOST buffer (tests). */
 int car_debug_control_tokens(car_ctx* ctx, int32_t k, float* host_out, int64_t max_elems);
 

@@ -122,3 +122,28 @@ def test_first_valid_position_of_left_padded_masks():
     assert first_valid_position(m) == 40
     _, masks = synth.text_embeddings(64, 120, 8)
     assert first_valid_position(masks) == 120 - int(masks.sum(dim=1).max())
+
+
+def test_prompt_window_rule_as_properties():
+    """The prefill window of car_generate (grain 16) and car_score (grain 32), seen through the host-only car_debug_prompt_window: the pass computes rows
+    [t0, T).  t0 is the LARGEST multiple of the grain that is <= min(clamp(first_valid, 0, T), T - 8), so that no valid row is left out, Tv = T - t0 stays a
+    multiple of 8 and at least 8; a T that is not a multiple of 8 above 8 has no window."""
+    import ctypes
+    from controlar_amd import _lib as L
+    lib = L.load()
+    t0, Tv = ctypes.c_int32(-7), ctypes.c_int32(-7)
+    for grain in (16, 32):
+        for T in (8, 12, 16, 24, 120, 128, 256):
+            for fv in range(-1, T + 2):
+                assert lib.car_debug_prompt_window(T, fv, grain, ctypes.byref(t0), ctypes.byref(Tv)) == 0
+                a, n = t0.value, Tv.value
+                assert a + n == T and n >= 8, (T, fv, grain, a, n)
+                if T in (8, 12):
+                    assert a == 0 and n == T, (T, fv, grain, a, n)
+                    continue
+                bound = min(max(0, min(fv, T)), T - 8)
+                assert a % grain == 0 and n % 8 == 0 and a <= max(fv, 0), (T, fv, grain, a, n)
+                assert a <= bound < a + grain, (T, fv, grain, a, n)      # a fits under the bound, the next multiple does not: maximality
+    for bad in (0, -16, 4, 12, 20):
+        assert lib.car_debug_prompt_window(120, 40, bad, ctypes.byref(t0), ctypes.byref(Tv)) != 0
+    assert lib.car_debug_prompt_window(120, 40, 16, None, ctypes.byref(Tv)) != 0
