@@ -126,7 +126,7 @@ static int sample_logits_impl(car_ctx* c, const float* logits, int32_t B, int32_
     if (rows) { if (rows_upload(c, rows, B, st)) return -1; p.rows = (const SampleRow*)c->rows_dev.p; }
     // out_tokens is indexed [i*n_new + step]: n_new = 1 and a zero step pointer keep it dense; the RNG step goes through row0, the cfg_interval test's through mix_step0
     HIPCHK(c, hipMemsetAsync(stepd, 0, 4, st));           // no host source buffer, no wait: the entry only enqueues
-    p.row0 = step * 65536; p.mix_step0 = step;
+    p.row0 = (int)((unsigned)step * 65536u); p.mix_step0 = step;      // modulo 2^32 (the counter word is unsigned): no signed overflow from step = 32768 up
     car_launch_sample_greedy(&p, st);
     fence_out(c, caller);
     HIPCHK(c, hipGetLastError());

@@ -800,6 +800,7 @@ __device__ inline void sample_greedy_block(const SampleP& p, int i, int step, bo
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int k = 1; k < nw; ++k) if (smv[k] > best || (smv[k] == best && smi[k] < bi)) { best = smv[k]; bi = smi[k]; }
+        if (bi >= p.V) bi = 0;      // no comparable logit (every one -inf or NaN): token 0, as the stochastic kernel — never an index a gather could not take
         p.out_tokens[(long)i * p.n_new + step] = bi;
         const int fb = p.forced ? p.forced[(long)i * p.n_new + step] : bi;
         p.cur_tok[i] = fb;
@@ -828,6 +829,14 @@ __device__ inline float philox_uniform(unsigned long long seed, unsigned a, unsi
     unsigned c0 = a, c1 = b, c2 = 0x243F6A88u, c3 = 0x85A308D3u, k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
     return (float)(c0 >> 8) * (1.0f / 16777216.0f);      // [0, 1)
+}
+// The sampler's key x = v * invT as ONE rounded fp32 product.  The stochastic kernel forms it three times (the LDS copy behind the filter and the maximum, the
+// chunk sums, the owner's walk) and subtracts the maximum from it; left to the default contraction the compiler turned some of those into fma(v, invT, -mx),
+// which exponentiates the UNROUNDED product against a rounded maximum.  At |x| ~ 1e6 (T <= 1e-5) the two differ by up to 0.125 in the exponent: the owner's
+// running sum then stayed below a target formed from the other sum, and the fallback returned the chunk's last token, a token of probability zero.
+__device__ inline float sample_key(float v, float invT) {
+#pragma clang fp contract(off)
+    return v * invT;
 }
 // exclusive prefix sum of one value per thread over a 1024-thread block (16 waves); returns the block total via `total`
 __device__ inline float block_excl_scan(float v, float* sm /* >= 34 floats */, float& total) {
@@ -868,7 +877,7 @@ __global__ __launch_bounds__(1024) void sample_stochastic_kernel(SampleP p, int 
         float v[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         if (j < p.V) { mixed4(j, v); if (lo) *(float4*)(lo + j) = make_float4(v[0], v[1], v[2], v[3]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] *= invT; }
+            for (int e = 0; e < 4; ++e) v[e] = sample_key(v[e], invT); }
         keys[j] = v[0]; keys[j + 1] = v[1]; keys[j + 2] = v[2]; keys[j + 3] = v[3];
     }
     __syncthreads();
@@ -949,7 +958,7 @@ __global__ __launch_bounds__(1024) void sample_stochastic_kernel(SampleP p, int 
     for (int j = j0; j < j0 + per && j < p.V; j += 4) {
         float v[4]; mixed4(j, v);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { const float x = v[e] * invT; if (x >= thr) loc += expf(x - mx); }
+        for (int e = 0; e < 4; ++e) { const float x = sample_key(v[e], invT); if (x >= thr) loc += expf(x - mx); }
     }
     float total; const float excl = block_excl_scan(loc, sm, total);
     const float target = philox_uniform(p.seed, rng_a, (unsigned)step) * total;
@@ -969,7 +978,7 @@ __global__ __launch_bounds__(1024) void sample_stochastic_kernel(SampleP p, int 
         for (int j = j0; j < j0 + per && j < p.V; j += 4) {
             float v[4]; mixed4(j, v);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { const float x = v[e] * invT; if (x >= thr) { run += expf(x - mx); last = j + e; if (pick < 0 && run > target) pick = j + e; } }
+            for (int e = 0; e < 4; ++e) { const float x = sample_key(v[e], invT); if (x >= thr) { run += expf(x - mx); last = j + e; if (pick < 0 && run > target) pick = j + e; } }
         }
         if (pick < 0) pick = last;                // rounding left the running sum at or below target: the chunk's last kept token
         tok_s = pick;
