@@ -113,6 +113,14 @@ struct VqOps {
     }
 };
 
+// Channel widths the helper kernels of ops.hip cannot take, refused here because car_create does not look at the VQ widths: GroupNorm(32) needs whole groups, its
+// stage-1 partials live in ws[8], sized below for 512 channels per pixel chunk, and conv_out reads 8 (fp32: 4) channels per load.  Returns the offending width or 0.
+static int vq_bad_width(const std::vector<VqItem>& layout, int last_c) {
+    int bad = (last_c > 512 || last_c % 32) ? last_c : 0;
+    for (auto& it : layout) for (int ch : {it.cin, it.cout}) if (ch > 512 || ch % 32) bad = ch;
+    return bad;
+}
+
 // VQModel.encode (vq_model.py:41-46) -> min_encoding_indices: img fp32 NCHW [B,3,H,W] (H, W multiples of 16) -> tokens int32 [B, (H/16)(W/16)]
 extern "C" int car_vq_encode(car_ctx* c, const float* img, int32_t B, int32_t H, int32_t W, int32_t* out_tokens, void* stream_) {
     if (c && check_sticky(c)) return -1;
@@ -126,6 +134,7 @@ extern "C" int car_vq_encode(car_ctx* c, const float* img, int32_t B, int32_t H,
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
     int last_c = 0;
     const std::vector<VqItem> layout = vq_enc_layout(g, &last_c);
+    if (const int ch = vq_bad_width(layout, last_c)) FAIL(c, "car_vq_encode: %d channels unsupported (every GroupNorm width must be a multiple of 32, at most 512)", ch);
     const int hh = H / div, ww = W / div, HW0 = hh * ww, HWp = (int)rup(HW0, 32);
     size_t max_el = (size_t)H * W * g.vq_ch;
     { size_t hw = (size_t)H * W; for (auto& it : layout) { if (it.kind == 3) hw /= 4; size_t cc = it.cin > it.cout ? it.cin : it.cout; if (hw * cc > max_el) max_el = hw * cc; } }
@@ -166,6 +175,7 @@ extern "C" int car_vq_decode(car_ctx* c, const int32_t* tokens, int32_t B, int32
     hipStream_t caller = (hipStream_t)stream_, st = c->stream;
     int last_c = 0;
     const std::vector<VqItem> layout = vq_layout(g, &last_c);
+    if (const int ch = vq_bad_width(layout, last_c)) FAIL(c, "car_vq_decode: %d channels unsupported (every GroupNorm width must be a multiple of 32, at most 512)", ch);
     const int nup = g.vq_n_mult - 1, Hf = hh << nup, Wf = ww << nup;
     // largest activation (elements per image): track through the layout
     size_t max_el = 0; { int ch = g.vq_ch * g.vq_ch_mult[g.vq_n_mult - 1]; size_t hw = (size_t)hh * ww; max_el = hw * (ch > g.z_channels ? ch : g.z_channels);

@@ -114,7 +114,7 @@ template <> __device__ inline void st4<bf16_t>(bf16_t* p, const float (&v)[4]) {
 }
 
 // one block per row; each thread owns groups of 4 consecutive columns (D % 4 == 0), values stay in registers
-// (up to 4 groups per thread: D <= 16 * blockDim)
+// (up to 4 groups per thread: D <= 16 * blockDim).  Preconditions (not checked by the void launcher): D % 4 == 0 and D <= 16384; parts_stride % 4 == 0.
 template <typename T>
 __global__ __launch_bounds__(1024) void rmsnorm_kernel(NormP p) {
     __shared__ float sm[20];
@@ -350,6 +350,13 @@ extern "C" void car_launch_vit_assemble(int mode, const void* tok, const void* c
 // ------------------------------------------------------------------ GroupNorm(32, eps) [+ swish] on NHWC (vq_model.py:355-363)
 // stage 1: per (b, pixel-chunk) per-channel partial sums (coalesced full-row reads); stage 2: fixed-order
 // reduction to (mean, rstd) per (b, group) in double; stage 3: apply.
+// Domain: var = q/n - mean^2 from SINGLE-PASS fp32 partials, so the relative error of rstd grows with (q/n) / var = 1 + (mean/std)^2: it is bounded by
+// L 2^-24 (q/n) / (var + eps), L the add chain of one partial (at most 257).  The statistics are fp32-grade up to mean/std ~ 4 (measured worst relative error of rstd on Gaussian
+// data: 9e-8 at mean/std 0, 3e-6 at 4, 4e-5 at 16) and lose roughly a digit per factor 4 beyond it (experiments/ops_check.hip, dense cases; measured error / bound ratios in profiles/ops_check_quick.txt).  The summation
+// order is fixed by the recorded digests and the bit-identity tests of the exact mode; do not "improve" it.
+// Preconditions (not checked by the void launchers): C % G == 0; `part` holds B * ceil(HW / 256) * 2 * C floats (the engine's workspace is sized for C <= 512 and
+// car_vq_encode / car_vq_decode refuse wider layers); the two routes of stage 3 (gn_apply_vec_kernel, or gn_apply_kernel under CAR_GN_SCALAR / a pointer off 16
+// bytes) use __expf and expf: bit-equal without swish, each within one bf16 ulp of the rounded fp64 swish on at most 1 % of the elements with it.
 #define GN_CHUNK 256   // pixels per block in stage 1
 template <typename T>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const void* x_, float* part, int HW, int C) {
@@ -529,6 +536,8 @@ extern "C" void car_launch_vq_lookup(int mode, const int* tok, const float* cb, 
 
 // ------------------------------------------------------------------ conv_out 3x3 C->3 on NHWC input, fp32 NCHW output (vq_model.py:168,194)
 // weights packed [3][9][C]; one lane per output pixel, channels in the inner loop.
+// Precondition (not checked by the void launcher): C % 8 == 0 in bf16 mode, C % 4 == 0 in fp32 mode (16-byte activation loads); 27 * C floats of LDS, C <= 512.
+// The engine refuses other widths (engine_vq.hip, vq_bad_width).
 template <typename T> struct LdVec;
 template <> struct LdVec<bf16_t> { static constexpr int N = 8;
     __device__ static inline void ld(const bf16_t* p, float (&v)[8]) {
@@ -673,6 +682,8 @@ extern "C" void car_launch_conv_in3(int mode, const float* img, const void* w, c
 // ------------------------------------------------------------------ VectorQuantizer.forward arg-min (vq_model.py:216-232)
 // z NHWC T [npix, cd] ; both z and the codebook are l2-normalised (F.normalize eps 1e-12);
 // d_j = |z|^2 + |e_j|^2 - 2 z.e_j in fp32 ; token = first index of the minimum.  One block per pixel.
+// Precondition: cd <= 16 (z lives in 16 registers; car_vq_encode refuses a larger codebook_embed_dim).  Threads with no code (ncode < 256) and pixels whose
+// distances are all NaN keep the sentinel index 0x7fffffff through the folds, where every real index beats it at equal distance; the last fold maps it to 0.
 template <typename T>
 __global__ __launch_bounds__(256) void vq_argmin_kernel(const void* z_, const float* cb, int* tok, int cd, int ncode) {
     __shared__ float smv[4]; __shared__ int smi[4];
@@ -702,6 +713,7 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const void* z_, const fl
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int k = 1; k < 4; ++k) if (smv[k] < best || (smv[k] == best && smi[k] < bi)) { best = smv[k]; bi = smi[k]; }
+        if (bi >= ncode) bi = 0;    // no distance compared below +inf (a NaN or inf in z makes every one NaN): torch.argmin's index 0 — never the sentinel, which no gather could take
         tok[pix] = bi;
     }
 }

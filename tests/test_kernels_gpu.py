@@ -117,3 +117,29 @@ def test_bf16_decode_kernels_against_exact_integer_references():
     out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
     assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout
+
+
+def test_helper_kernels_against_exact_and_fp64_references():
+    """ops.hip and t5.hip (experiments/ops_check.hip, quick mode, built with -DCAR_DEV_KNOBS so that CAR_GN_SCALAR is live; the harness sets it per case): the helper
+    kernels in front of every stage through their real car_launch_* entry points — GroupNorm (gn_partial / gn_partial_vec / gn_finalize / gn_apply / gn_apply_vec),
+    vq_argmin, vq_lookup, conv_out (scalar and MFMA form), conv_in3, rmsnorm_kernel, layernorm_kernel, swiglu, swiglu_parts, t5_gated_act, convert, build_text,
+    gather_rows, label_index, t5_prep, patchify, vit_assemble, ctrl_scale_rows, row_mix_scale, set_pos_step, advance.  Every case on one arena poisoned with 0xff,
+    256 guard bytes between the buffers, the WHOLE arena compared with the expected image (outputs, unchanged inputs, guards), two images / several rows with
+    different data, both modes, two runs with equal bits, every pointer's byte extent asserted on the host before the launch.  No tolerance wherever the arithmetic
+    is exact: stage-1 GroupNorm partials of hashed integers for HW in {1, 64, 255, 256, 257, 600} x C in {32 .. 512, 96, 320} (vector == scalar kernel), sign rows
+    +-2^a(b, g) through stages 2 and 3 (mean 0, rstd 2^-a, y = +-gamma + beta; CAR_GN_SCALAR bit-equal to the vector route; have_part; y == nullptr; the stride
+    loop twice); vq_argmin on a dyadic codebook (distances exactly 0 / 2 / 4) with the winner at 0 / 63 / 64 / 255 / 256 / 257 / ncode - 1 for ncode in {1, 5, 64,
+    255, 256, 257, 1000, 16384}, exact ties (the lower index wins across lanes, waves and iterations), an all-zero row, and NaN / inf rows whose token must be 0
+    — torch.argmin's answer; the kernel used to return 0x7fffffff there; conv_out on integer operands with asymmetric weights (MFMA form == scalar form == the
+    integer convolution, H x W in {1x1, 5x7, 16x16, 17x33, 31x16}); conv_in3 with 257 -> 256 and 259 -> 260; rmsnorm_kernel for D in {64 .. 8192} (the second
+    register group included) with gather, the three add modes, split-K parts of 1 / 3 / 4 / 5 / 8 / 9 slices, h_out and xn present or absent: every row bit-equal
+    to the row of one of the three candidate rstd values, sign rows to the only one; layernorm on sign rows around an integer centre; the block-16 interleaved
+    SwiGLU / GELU layout on saturated integer gates; all 65536 bf16 patterns (x 17 low halves) through convert against the harness's own rounding; clamps, flags,
+    -0, NaN payloads, windows and dyadic bicubic weights in the copy and index kernels.  Bounds are derived in the harness header, never measured: swish (expf's
+    ulp), dense GroupNorm statistics at mean/std 0 / 4 / 16 against a two-pass fp64 reference (profiles/ops_check_quick.txt holds the measured ratios), dense
+    argmin (the token within (2 cd + 16) 2^-23 of the fp64 minimum, equal to the fp64 argmin wherever the runner-up is further away), vq_lookup, layernorm,
+    SwiGLU (gemm_check.hip's rule)."""
+    exe = _build("ops_check", extra=("-DCAR_DEV_KNOBS",))
+    out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout[-3000:] + out.stderr[-1000:]
+    assert "BITS DIFFER" not in out.stdout and "FAIL" not in out.stdout

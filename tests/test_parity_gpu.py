@@ -240,6 +240,16 @@ def test_error_paths_raise():
     with pytest.raises(RuntimeError):
         eng.generate(cs["emb"].cuda(), 4096, _mask(cs))          # beyond block_size
     eng.close()
+    # a VQ width the helper kernels cannot take (GroupNorm(32) groups, its 512-channel workspace, conv_out's 8-channel loads) is refused before any launch
+    from controlar_amd import config as C, synth
+    cfg = C.tiny_t2i(64, "canny")
+    cfg.vq = C.VQConfig(codebook_size=cfg.vq.codebook_size, z_channels=64, ch=36, ch_mult=(1,), num_res_blocks=1)
+    eng = Engine(cfg, "bf16"); eng.load_state_dict(synth.vq_state_dict(cfg.vq, seed=3), finalize=True)
+    with pytest.raises(RuntimeError, match="36 channels"):
+        eng.vq_decode(torch.zeros(1, 64, dtype=torch.int32), 8, 8)
+    with pytest.raises(RuntimeError, match="36 channels"):
+        eng.vq_encode(torch.zeros(1, 3, 16, 16).cuda())
+    eng.close()
 
 
 def test_two_chain_decode_large_batch():
